@@ -30,10 +30,14 @@ Extra objects:
                   per-launch durations measured with HIP events on the launch stream during the timed region
                   (vqs_profile_*), against the 2.5 PFLOP/s dense bf16 MFMA peak; `traffic` from the committed
                   rocprofv3 --pmc passes over this same command (profiles/gemm_traffic_<model>_b<batch>.json).
-  cpu_baseline -- the reference's own arithmetic (HF CLIPVisionModel + T5ForConditionalGeneration cast to bf16 as
-                  mm_utils.py:228 does, oracle/hf_reference.py) timed on the host cores: 1 warm-up + 3 repetitions on
-                  the first pair(s) of the same batch (rank 0, N = 1 only), the fp32 port beside it, and the three-way
+  cpu_baseline -- (--full only) the reference's own arithmetic (HF CLIPVisionModel + T5ForConditionalGeneration cast to
+                  bf16 as mm_utils.py:228 does, oracle/hf_reference.py) timed on the host cores: 1 warm-up + 3 repetitions
+                  on the first pair(s) of the same batch (rank 0, N = 1 only), the fp32 port beside it, and the three-way
                   |delta log P| table BASELINE.md §3 prescribes.
+  also         -- (--full only) short legs of the other BASELINE configurations, each in its own process.
+
+A plain run (no --full) sets up, warms up, times the steps and prints its line; --dump-outputs DIR also writes the last
+timed step's outputs (label log-probs, scores) as DIR/<name>.npy, float32, from the same seeded inputs every run.
 """
 from __future__ import annotations
 
@@ -284,15 +288,15 @@ def traffic_stamp_matches(tj):
 
 ALSO_LEGS = {
     # name: (argv after the interpreter, what BASELINE.json config it is)
-    "xl": (["bench.py", "--model", "clip-flant5-xl", "--steps", "5", "--warmup", "2", "--cpu-pairs", "0", "--also", "none", "--parity-only", "32"],
+    "xl": (["bench.py", "--full", "--model", "clip-flant5-xl", "--steps", "5", "--warmup", "2", "--cpu-pairs", "0", "--also", "none", "--parity-only", "32"],
            "configs[1]: clip-flant5-xl bf16, batch=256 synthetic 224x224 + 32-tok prompts; + its own 32-pair |delta log P| table"),
-    "genai1600": (["bench.py", "--workload", "genai1600", "--buckets", "6", "--warmup", "1", "--cpu-pairs", "0", "--also", "none", "--parity-only", "32"],
+    "genai1600": (["bench.py", "--full", "--workload", "genai1600", "--buckets", "6", "--warmup", "1", "--cpu-pairs", "0", "--also", "none", "--parity-only", "32"],
                   "configs[2]: clip-flant5-xxl, GenAI-Bench-1600 stand-in, 6 of its 38 length buckets; + a 32-pair |delta log P| table over its "
                   "shortest and longest batch (ragged prompts, padded and masked)"),
-    "qwen": (["bench.py", "--model", "qwen2.5-vl-7b", "--steps", "3", "--warmup", "1", "--cpu-pairs", "0", "--also", "none", "--parity-only", "32"],
+    "qwen": (["bench.py", "--full", "--model", "qwen2.5-vl-7b", "--steps", "3", "--warmup", "1", "--cpu-pairs", "0", "--also", "none", "--parity-only", "32"],
              "configs[4]: qwen2.5-vl-7b, 8-frame video samples (range-safe fp16 forms + precise tail); + |delta log P(answer)| of 32 samples against the fp32 "
              "oracle evaluated on the device, held to the 1e-3 bound (exit 3)"),
-    "bf16_operands": (["bench.py", "--steps", "3", "--warmup", "1", "--cpu-pairs", "0", "--also", "none", "--opt", "vit_fp16=0", "--opt", "enc_fp16=0", "--opt", "dec_fp16=0", "--parity-only", "32"],
+    "bf16_operands": (["bench.py", "--full", "--steps", "3", "--warmup", "1", "--cpu-pairs", "0", "--also", "none", "--opt", "vit_fp16=0", "--opt", "enc_fp16=0", "--opt", "dec_fp16=0", "--parity-only", "32"],
                       "INFORMATIONAL, allowed to exceed the bound: the headline configuration with every 16-bit tensor of the vision tower and the T5 encoder "
                       "in bf16 (options vit_fp16 = 0, enc_fp16 = 0, dec_fp16 = 0: the reference's dtype, mm_utils.py:228; rounds 1-3's arithmetic there) -- throughput and "
                       "the 32-pair |delta log P| table next to the main line's fp16 forms"),
@@ -417,9 +421,16 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=256, help="pairs per GPU per step")
     ap.add_argument("--workload", default="synthetic", choices=["synthetic", "genai1600"])
     ap.add_argument("--pairs", type=int, default=0, help="fixed total number of pairs over all ranks (BASELINE configs[3]: 100000)")
-    ap.add_argument("--cpu-pairs", type=int, default=4, help="pairs in the CPU reference sample (BASELINE.md section 3: 4 at XXL; 0 = skip the cpu_baseline leg)")
-    ap.add_argument("--also", default="auto", help="extra short legs reported under \"also\" (the other BASELINE configs): comma list of "
-                    "xl,genai1600,qwen,pipeline,config0; auto = all of them for the default single-GPU XXL run, none otherwise; none = off")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure as well: the cpu_baseline leg with its |delta log P| "
+                    "tables (--cpu-pairs defaults to 4) and the extra legs (--also defaults to auto); a plain run only sets up, warms up, "
+                    "times the steps and prints its line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step computed "
+                    "(label log-probs and scores of this rank's batch) as DIR/<name>.npy in float32")
+    ap.add_argument("--cpu-pairs", type=int, default=None, help="pairs in the CPU reference sample (BASELINE.md section 3: 4 at XXL; 0 = skip the "
+                    "cpu_baseline leg); default 4 with --full, 0 without")
+    ap.add_argument("--also", default=None, help="extra short legs reported under \"also\" (the other BASELINE configs): comma list of "
+                    "xl,genai1600,qwen,pipeline,config0; auto = all of them for the default single-GPU XXL run, none otherwise; none = off; "
+                    "default auto with --full, none without")
     ap.add_argument("--buckets", type=int, default=0, help="genai1600: time only this many length buckets, evenly spaced over the sorted workload (0 = all 38)")
     ap.add_argument("--cpu-emulation", action="store_true", help="also run the rounding-matched CPU oracle on pair 0 (~40 s at XXL)")
     ap.add_argument("--cpu-reps", type=int, default=3, help="timed repetitions of the CPU reference after 1 warm-up (BASELINE.md section 3: >= 3; a 4-pair XXL pass is ~50 s)")
@@ -430,7 +441,33 @@ def parse_args(argv=None):
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="execution-form option of include/vqs.h vqs_set_option (e.g. gemm_variant=6, tile_order:20480x4096=520); "
                          "every form computes the same function -- for A/B runs, recorded in config.options")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.cpu_pairs is None:
+        args.cpu_pairs = 4 if args.full else 0
+    if args.also is None:
+        args.also = "auto" if args.full else "none"
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays: {name: tensor} -> out_dir/<name>.npy, float32 (float64 kept).  Above `limit` bytes in all, every array is cut to the
+    same fixed, seeded sample of its flattened elements (the positions depend only on its size), so two runs stay comparable."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        host[name] = a.double().numpy() if a.dtype == torch.float64 else a.float().numpy()
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > limit:
+            keep = max(1, int(a.size * limit / total))
+            pos = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def main():
@@ -442,17 +479,20 @@ def main():
             raise SystemExit("the Qwen2.5-VL bench line is single-GPU (replicas need no collective: run one process per GPU)")
         sys.argv = [os.path.join(ROOT, "tools", "bench_qwen.py"), "--model", args.model, "--steps", str(args.steps), "--warmup",
                     str(args.warmup), "--batch", str(min(args.batch, 64)), "--cpu-samples", str(min(args.cpu_pairs, 1)),
-                    "--decode-steps", "16",          # + the cached decode step (generation beyond the first token), reported under "decode"
+                    "--decode-steps", "16" if args.full else "0",   # --full: + the cached decode step (generation beyond the first token), under "decode"
                     "--parity-samples", str(max(args.parity_only, 0))]
+        if args.dump_outputs:
+            sys.argv += ["--dump-outputs", args.dump_outputs]
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_qwen
         return bench_qwen.main()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU, rendezvous on 127.0.0.1
+        # plain `python bench.py --gpus N`: launch the ranks as child processes -- one rank per GPU, rendezvous on 127.0.0.1
+        import subprocess
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -564,6 +604,8 @@ def main():
         final = local
     barrier()
     elapsed_local = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and lp is not None:
+        write_outputs(args.dump_outputs, {"label_logprobs": lp, "scores": sc})     # what the last timed step handed its caller
     step_ms = [round(step_ev[i].elapsed_time(step_ev[i + 1]), 2) for i in range(len(jobs))] if step_ev else None
     eng.profile(False)
     gemm_bytes = eng.profile_bytes()

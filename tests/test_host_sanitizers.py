@@ -23,7 +23,9 @@ def test_host_abi_under_asan_and_ubsan():
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "t2v_metrics_amd", "csrc"), "-j4"], stdout=subprocess.DEVNULL)
     out = os.path.join(ROOT, "build", "asan")
     os.makedirs(out, exist_ok=True)
-    san = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-O1", "-g", "-std=c++17"]
+    # host code only: -fno-gpu-sanitize keeps the sanitizers out of every device compilation hipcc does next to it
+    san = ["-fsanitize=address,undefined", "-fno-gpu-sanitize", "-Wno-unused-command-line-argument", "-fno-omit-frame-pointer", "-O1", "-g",
+           "-std=c++17"]
     csrc = os.path.join(ROOT, "t2v_metrics_amd", "csrc")
     for src in ("vqs_api.cpp", "vqs_qwen.cpp"):
         subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-fPIC", *san, "-c", os.path.join(csrc, src), "-o",
@@ -31,7 +33,7 @@ def test_host_abi_under_asan_and_ubsan():
     subprocess.check_call([CLANG, *san, "-I" + os.path.join(ROOT, "include"), "-c",
                            os.path.join(ROOT, "tests", "cabi", "host_abi_exercise.cpp"), "-o", os.path.join(out, "driver.o")])
     exe = os.path.join(out, "host_abi_exercise")
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-fsanitize=address,undefined", os.path.join(out, "driver.o"),
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-fsanitize=address,undefined", "-fno-gpu-sanitize", os.path.join(out, "driver.o"),
                            os.path.join(out, "vqs_api.cpp.o"), os.path.join(out, "vqs_qwen.cpp.o"), *dev_objs, "-o", exe],
                           stderr=subprocess.DEVNULL)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")

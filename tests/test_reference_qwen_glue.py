@@ -1,16 +1,16 @@
-"""The Qwen2.5-VL wrapper's scoring tail against the reference's OWN ``Qwen2VLModel.forward`` / ``forward_with_trace``
-(/root/reference/t2v_metrics/models/vqascore_models/qwen2vl_model.py:165-301, 303-493), run here from where it lies.
+"""The Qwen2.5-VL wrapper's scoring tail against the reference's OWN ``Qwen2VLModel.forward`` / ``forward_with_trace`` /
+``generate`` (the reference's models/vqascore_models/qwen2vl_model.py:165-301, 303-493, 495-563), through their recorded outputs
+(tests/golden/reference_qwen_glue.json).
 
-The reference methods are driven without a checkpoint: an instance made with ``object.__new__`` gets a stub processor (chat
+The reference methods were driven without a checkpoint: an instance made with ``object.__new__`` got a stub processor (chat
 template = this package's ``chat_prompt``, tokenizer = the same fake tokenizer our wrapper is given) and a stub
 ``model.generate`` that is plain greedy decoding over a SCRIPTED language model -- logits are a seeded function of (prompt text
 ids, tokens generated so far).  Our wrapper gets the same scripted model behind its engine interface.  What is compared is what
 the two wrappers do with identical generations: which score rows they read (last-n, one earlier after a trailing special
 token, first-n for ``score_position="start"``), truncation to what was generated, temperature, the geometric mean, the trace
-fields, and the errors.
-
-Skips when /root/reference is absent (the GPU box)."""
-import types
+fields, and the errors."""
+import json
+import os
 import zlib
 
 import numpy as np
@@ -20,8 +20,10 @@ import torch
 import t2v_metrics_amd as t2v
 from t2v_metrics_amd.models.vqascore_models.qwen25vl_model import chat_prompt
 from t2v_metrics_amd.qwen import get_qwen_config
-from tests.reference_loader import reference_module
 from tests.test_qwen_host import SPECIALS, FakeQwenTokenizer
+
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_qwen_glue.json")) as _f:
+    REF = json.load(_f)
 
 CFG = get_qwen_config("qwen-tiny")
 PADS = (SPECIALS["<|image_pad|>"], SPECIALS["<|video_pad|>"])
@@ -67,75 +69,18 @@ class ScriptedEngine:
         return torch.stack([scripted_logits(r, g) for r, g in zip(state["rows"], state["gen"])])
 
 
-class Inputs(dict):
-    """What the HF processor returns, as far as the reference touches it: mapping + attribute access + ``.to``."""
-
-    __getattr__ = dict.__getitem__
-
-    def to(self, device):
-        return self
-
-
-class StubProcessor:
-    def __init__(self, tok):
-        self.tokenizer = tok
-
-    def apply_chat_template(self, messages, tokenize=False, add_generation_prompt=True):
-        assert tokenize is False and add_generation_prompt is True and len(messages) == 1 and messages[0]["role"] == "user"
-        medium, text = messages[0]["content"]
-        return chat_prompt(text["text"], "<|video_pad|>" if medium["type"] == "video" else "<|image_pad|>")
-
-    def batch_decode(self, rows, skip_special_tokens=True, clean_up_tokenization_spaces=False):
-        return [self.tokenizer.decode(r, skip_special_tokens=skip_special_tokens) for r in rows]
-
-    def __call__(self, text, images=None, videos=None, padding=True, return_tensors="pt", do_resize=False, **kw):
-        assert len(text) == 1 and (images is None) != (videos is None) and do_resize is False
-        return Inputs(input_ids=torch.tensor([self.tokenizer.encode(text[0], add_special_tokens=False)]))
-
-
-class StubGenerator:
-    """HF ``generate(do_sample=False, output_scores=True, return_dict_in_generate=True)`` over the scripted LM: greedy, stops after
-    emitting one of ``stop_ids`` (generation_config.eos_token_id), ``scores[t]`` = the [1, vocab] row token t was picked from."""
-
-    def __init__(self, stop_ids):
-        self.stop_ids = list(stop_ids)
-        self.calls = 0
-
-    def generate(self, input_ids, max_new_tokens, do_sample, temperature=1.0, output_scores=False, return_dict_in_generate=False):
-        assert temperature == 1.0 and do_sample is False and output_scores == return_dict_in_generate
-        self.calls += 1
-        prompt, gen, scores = input_ids[0].tolist(), [], []
-        for _ in range(max_new_tokens):
-            row = scripted_logits(prompt, gen)
-            scores.append(row[None])
-            gen.append(int(row.argmax()))
-            if gen[-1] in self.stop_ids:
-                break
-        if not return_dict_in_generate:                       # the free-form generate() call: just the sequences
-            return torch.tensor([prompt + gen])
-        return types.SimpleNamespace(sequences=torch.tensor([prompt + gen]), scores=tuple(scores))
-
-
-def _pair(tmp_path, stop_ids=(), **special):
-    """(our wrapper, the reference's wrapper) over the same scripted LM, tokenizer and stop ids."""
-    ref = reference_module("models.vqascore_models.qwen2vl_model", optional=("qwen_vl_utils", "decord", "cv2"))
-
-    def process_vision_info(messages, return_video_kwargs=False):
-        medium = messages[0]["content"][0]
-        if medium["type"] == "video":
-            return None, [medium["video"]], {"fps": [2.0]}
-        return [medium["image"]], None, {}
-    ref.process_vision_info = process_vision_info
-
+def _ours(stop_ids=(), **special):
+    """Our wrapper over the scripted LM, with the tokenizer specials and stop ids the reference's run was given."""
     tok = Tokenizer(CFG.text.vocab)
     for k, v in special.items():
         setattr(tok, k, v)
-    theirs = object.__new__(ref.Qwen2VLModel)                 # no checkpoint: __init__ / load_model never run
-    theirs.model_name, theirs.device, theirs.model_info = "qwen2.5-vl-7b", "cpu", {"fps": 8.0}
-    theirs.processor, theirs.model = StubProcessor(tok), StubGenerator(stop_ids)
     ours = t2v.VQAScore(model="qwen2.5-vl-7b", device="cpu", config=CFG, engine=ScriptedEngine(), tokenizer=tok).model
     ours._gen_eos_ids = list(stop_ids)
-    return ours, theirs
+    return ours
+
+
+def _ref(values):
+    return torch.tensor(values, dtype=torch.float32)
 
 
 @pytest.fixture()
@@ -168,37 +113,38 @@ def _first_tokens(texts, n):
 @pytest.mark.parametrize("answer", ["Yes", "Yes indeed", "Yes it certainly is"])
 @pytest.mark.parametrize("budget", [1, 2, 3, 5])
 def test_forward_reads_the_same_score_rows_as_the_reference(tmp_path, media, answer, budget, capsys):
-    ours, theirs = _pair(tmp_path)
+    ours = _ours()
     for temperature in (1.0, 0.5, 2.5):
         a = ours.forward(media, TEXTS, answer_template=answer, max_new_tokens=budget, temperature=temperature)
-        b = theirs.forward(media, TEXTS, answer_template=answer, max_new_tokens=budget, temperature=temperature)
+        b = _ref(REF["forward"]["%s|%d|%g" % (answer, budget, temperature)])
         assert a.shape == b.shape == (3,) and a.dtype == b.dtype == torch.float32
         assert torch.allclose(a, b, rtol=2e-6, atol=1e-12), (a, b)
-    capsys.readouterr()                                        # the reference prints a warning when it truncates the answer
+    capsys.readouterr()
 
 
 def test_trailing_special_token_shifts_the_window_in_both(tmp_path, media):
     """A generation that ENDS in eos / bos / pad is scored one row earlier (:239-256); one that is ONLY the special token has nothing
     left and raises the same error in both."""
     g = _first_tokens(TEXTS, 3)
+    assert g == REF["first_tokens"]                            # the script the reference was run on
+    ref = REF["trailing_special"]
     # sample 0 stops at its 3rd token, sample 1 at its 2nd (eos), sample 2 never
     assert len({g[0][2], g[1][1]}) == 2 and g[0][2] not in g[0][:2] + g[2] and g[1][1] not in g[1][:1] + g[2] + g[0][:2]
-    ours, theirs = _pair(tmp_path, stop_ids=(g[0][2], g[1][1]), eos_token_id=g[1][1], pad_token_id=g[0][2])
+    ours = _ours(stop_ids=(g[0][2], g[1][1]), eos_token_id=g[1][1], pad_token_id=g[0][2])
     for answer in ("Yes", "Yes indeed", "Yes it certainly is"):
         a = ours.forward(media, TEXTS, answer_template=answer, max_new_tokens=4)
-        b = theirs.forward(media, TEXTS, answer_template=answer, max_new_tokens=4)
+        b = _ref(ref["eos_pad|" + answer])
         assert torch.allclose(a, b, rtol=2e-6, atol=1e-12), (answer, a, b)
     # the stop id is what HF generate stops at, the special-token rule is the TOKENIZER's: a stop id that is not a tokenizer
     # special is scored like any other last token
-    ours, theirs = _pair(tmp_path, stop_ids=(g[0][2], g[1][1]), eos_token_id=g[1][1])
+    ours = _ours(stop_ids=(g[0][2], g[1][1]), eos_token_id=g[1][1])
     a = ours.forward(media, TEXTS, answer_template="Yes indeed", max_new_tokens=4)
-    b = theirs.forward(media, TEXTS, answer_template="Yes indeed", max_new_tokens=4)
-    assert torch.allclose(a, b, rtol=2e-6, atol=1e-12)
-    # only a special token generated: nothing to score
-    ours, theirs = _pair(tmp_path, stop_ids=(g[0][0],), bos_token_id=g[0][0])
-    for m in (ours, theirs):
-        with pytest.raises(ValueError, match="No content tokens to score after removing special tokens"):
-            m.forward(media[:1], TEXTS[:1], max_new_tokens=3)
+    assert torch.allclose(a, _ref(ref["eos_only|Yes indeed"]), rtol=2e-6, atol=1e-12)
+    # only a special token generated: nothing to score -- the reference raised the same error
+    ours = _ours(stop_ids=(g[0][0],), bos_token_id=g[0][0])
+    with pytest.raises(ValueError, match="No content tokens to score after removing special tokens") as err:
+        ours.forward(media[:1], TEXTS[:1], max_new_tokens=3)
+    assert str(err.value) == ref["bos_only_error"]
 
 
 def _same_trace(a, b):
@@ -224,50 +170,53 @@ def _same_trace(a, b):
 @pytest.mark.parametrize("score_position", ["end", "start"])
 def test_forward_with_trace_is_the_references(tmp_path, media, score_position, capsys):
     g = _first_tokens(TEXTS, 3)
-    for stops, special in (((), {}), ((g[0][2], g[1][1]), {"eos_token_id": g[1][1], "pad_token_id": g[0][2]})):
-        ours, theirs = _pair(tmp_path, stop_ids=stops, **special)
+    assert g == REF["first_tokens"]
+    for si, (stops, special) in enumerate((((), {}), ((g[0][2], g[1][1]), {"eos_token_id": g[1][1], "pad_token_id": g[0][2]}))):
+        ours = _ours(stop_ids=stops, **special)
         for answer, budget, temperature in (("Yes", 1, 1.0), ("Yes indeed", 4, 0.7), ("Yes it certainly is", 2, 1.0),
                                             ("Yes it certainly is", 6, 1.9)):
             pa, ta = ours.forward_with_trace(media, TEXTS, answer_template=answer, max_new_tokens=budget, temperature=temperature,
                                              score_position=score_position)
-            pb, tb = theirs.forward_with_trace(media, TEXTS, answer_template=answer, max_new_tokens=budget, temperature=temperature,
-                                               score_position=score_position)
+            theirs = REF["forward_with_trace"]["%s|%d|%s|%d|%g" % (score_position, si, answer, budget, temperature)]
+            pb, tb = _ref(theirs["scores"]), theirs["traces"]
             assert torch.allclose(pa, pb, rtol=2e-6, atol=1e-12) and len(ta) == len(tb) == 3
             for x, y in zip(ta, tb):
-                _same_trace(x, y)
+                _same_trace(json.loads(json.dumps(x)), y)
     capsys.readouterr()
-    for m in _pair(tmp_path):
-        with pytest.raises(AssertionError, match="score_position must be"):
-            m.forward_with_trace(media[:1], TEXTS[:1], score_position="middle")
-        with pytest.raises(AssertionError, match="must match"):
-            m.forward(media, TEXTS[:2])
+    m, errs = _ours(), REF["errors"]
+    with pytest.raises(AssertionError, match="score_position must be"):
+        m.forward_with_trace(media[:1], TEXTS[:1], score_position="middle")
+    with pytest.raises(AssertionError, match="must match"):
+        m.forward(media, TEXTS[:2])
+    assert "score_position must be" in errs["score_position_middle"] and "must match" in errs["forward_count_mismatch"]
 
 
 def test_one_generation_per_pair_in_the_reference_one_tower_pass_per_medium_here(tmp_path, media):
-    ours, theirs = _pair(tmp_path)
+    ours, theirs = _ours(), REF["four_pairs"]
     seen = []
     enc = ours.engine.encode_vision
     ours.engine.encode_vision = lambda patches, grids: (seen.append(list(grids)), enc(patches, grids))[1]
     images, texts = [media[0]] * 3 + [media[1]], TEXTS + ["a fourth caption"]
-    a, b = ours.forward(images, texts), theirs.forward(images, texts)
-    assert torch.allclose(a, b, rtol=2e-6, atol=1e-12)
-    assert theirs.model.calls == 4 and sum(len(g) for g in seen) == 2          # 4 generate() calls there; 2 media encoded here
+    a = ours.forward(images, texts)
+    assert torch.allclose(a, _ref(theirs["values"]), rtol=2e-6, atol=1e-12)
+    assert theirs["generate_calls"] == 4 and sum(len(g) for g in seen) == 2    # 4 generate() calls there; 2 media encoded here
 
 
 def test_greedy_generate_returns_the_references_strings(tmp_path, media):
     """generate() (:495-563) with temperature 0: the text is the whole user turn, greedy until a stop id or the budget, decoded without
     special tokens and stripped."""
     g = _first_tokens(TEXTS, 3)
-    for stops, special in (((), {}), ((g[0][2], g[1][1]), {"eos_token_id": g[1][1]})):
-        ours, theirs = _pair(tmp_path, stop_ids=stops, **special)
+    assert g == REF["first_tokens"]
+    for si, (stops, special) in enumerate((((), {}), ((g[0][2], g[1][1]), {"eos_token_id": g[1][1]}))):
+        ours = _ours(stop_ids=stops, **special)
         questions = [f'Does this figure show "{t}"? Please answer Yes or No.' for t in TEXTS]     # so that _first_tokens' script applies
         for budget in (1, 3, 7):
             a = ours.generate(media, questions, max_new_tokens=budget)
-            b = theirs.generate(media, questions, max_new_tokens=budget)
+            b = REF["generate"]["%d|%d" % (si, budget)]
             assert a == b and len(a) == 3 and all(isinstance(x, str) for x in a)
         if stops:                                                                                  # stopped early where the script says so
             full = ours.generate(media, questions, max_new_tokens=7)
             assert len(full[0].split()) <= 3 and len(full[1].split()) <= 2 and len(full[2].split()) == 7
-    for m in _pair(tmp_path):
-        with pytest.raises(AssertionError, match="must match"):
-            m.generate(media, TEXTS[:1])
+    with pytest.raises(AssertionError, match="must match"):
+        _ours().generate(media, TEXTS[:1])
+    assert "must match" in REF["errors"]["generate_count_mismatch"]

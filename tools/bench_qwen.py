@@ -38,6 +38,7 @@ def main():
     ap.add_argument("--tail", type=int, default=1, help="option tail_precise (1 = the default: logits from the precise re-evaluation of the last position)")
     ap.add_argument("--fp16", type=int, default=1, help="option fp16 (1 = the default: the range-safe fp16 forms; 0 = bf16 everywhere, the reference's dtype)")
     ap.add_argument("--rope-fused", type=int, default=1, help="option rope_fused (1 = the default: q / k rotated inside the q|k|v epilogue under the fp16 forms)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's last-position logits as DIR/logits.npy (float32)")
     args = ap.parse_args()
     from t2v_metrics_amd.qwen.engine import QwenEngine
     cfg = get_qwen_config(args.model)
@@ -81,6 +82,9 @@ def main():
         logits = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        from bench import write_outputs
+        write_outputs(args.dump_outputs, {"logits": logits})
     eng.profile(False)
     n_gemm, gemm_ms, gemm_flops, gemm_bytes = eng.profile_read(reset=True)
     L = ids.shape[1]
