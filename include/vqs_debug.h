@@ -56,6 +56,19 @@ int vqs_debug_attention_f16(const void* d_q, const void* d_k, const void* d_v, v
                             int32_t B, int32_t H, int32_t S, float scale, void* stream);
 int vqs_debug_norm16(int32_t kind, float* d_x, const void* d_delta, const void* d_delta2, int32_t store_x, const void* d_w, const void* d_b,
                      void* d_out, int32_t M, int32_t D, float eps, int32_t types, void* stream);
+/* Single-launch test hooks of the Qwen2.5-VL row's shared prompt prefix (include/vqs_qwen.h vqs_qwen_score_suffix), on caller tensors;
+ * f16 = 1: IEEE fp16 tensors (the range-safe fp16 forms), 0: bf16.
+ *   vqs_debug_qwen_attention: the prefill's causal GQA attention (attn_fwd_hd_kernel): q [B, H, S, 128], k / v [B, Hkv, S, 128], out [B*S, H*128]
+ *   vqs_debug_qwen_attention_suffix: attn_suffix_hd_kernel, query rows [q0, S) only: q [B, H, Sq, 128] (row r = position q0 + r, Sq >= S - q0),
+ *     k / v [B, Hkv, S, 128], out [B*Sq, H*128]; q0 a multiple of 32
+ *   vqs_debug_qwen_kv_assemble: qwen_kv_assemble_kernel: dk / dv [B, Hkv, Lp + Ls, 128] from pk / pv [U, Hkv, Lp, 128] (medium media_idx[b];
+ *     outside [0, U): zero rows) and sk / sv [B, Hkv, Ls, 128] */
+int vqs_debug_qwen_attention(const void* d_q, const void* d_k, const void* d_v, void* d_out, const int32_t* d_key_len, int32_t B, int32_t H, int32_t Hkv,
+                             int32_t S, float scale, int32_t f16, void* stream);
+int vqs_debug_qwen_attention_suffix(const void* d_q, const void* d_k, const void* d_v, void* d_out, const int32_t* d_key_len, int32_t B, int32_t H,
+                                    int32_t Hkv, int32_t S, int32_t Sq, int32_t q0, float scale, int32_t f16, void* stream);
+int vqs_debug_qwen_kv_assemble(const void* d_pk, const void* d_pv, const void* d_sk, const void* d_sv, const int32_t* d_media_idx, void* d_dk, void* d_dv,
+                               int32_t B, int32_t U, int32_t Hkv, int32_t Lp, int32_t Ls, void* stream);
 /* Tap window: taps copy only the rows of `count` consecutive outer entries starting at `first` -- pairs for the T5 stacks
  * (rows [first*S, (first+count)*S) of an [B*S, W] tensor, the same fraction of a head-major [B, H, S, 64] or a [B*T, W] one),
  * images for the vision tower (so the window's pairs must reference images first .. first+count-1 in order, as the bench

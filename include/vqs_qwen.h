@@ -116,6 +116,35 @@ size_t vqs_qwen_decode_workspace_bytes(const vqs_qwen_handle* h, int32_t B);
 int vqs_qwen_decode(vqs_qwen_handle* h, const int32_t* d_ids, const int32_t* d_len, const float* d_cos, const float* d_sin, int32_t B,
                     int32_t Lmax, void* d_kv, size_t kv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Shared prompt prefix: several questions about one medium.  Every prompt about a medium starts with the same rows (chat header, vision run,
+ * <|vision_end|>) at the same M-RoPE positions, and the language model is causal, so every layer's K / V over those rows do not depend on the
+ * question.  vqs_qwen_prefix runs the layers over U prefixes of Lp rows once and keeps each layer's K (after the rotary embedding) and V in
+ * the caller-owned prefix store d_pkv (per layer K then V, each [U, t_kv_heads, Lp, 128], in the attention's operand format: bf16, or fp16
+ * behind the layer's proven scale under option "fp16" -- OPAQUE, for vqs_qwen_score_suffix of the same handle under the same option value).
+ * No final norm, no lm_head, no tail.  vqs_qwen_score_suffix then runs the layers over the B suffix rows [Lp, Lp + Ls) of each sample only,
+ * sample b behind the prefix of medium d_media_idx[b], and returns the d_logits [B, t_vocab] vqs_qwen_score gives for the whole sequences --
+ * BIT FOR BIT (DESIGN.md "Shared prompt prefix"); vqs_qwen_prefill_suffix also fills the decode cache exactly as vqs_qwen_prefill does, and
+ * vqs_qwen_decode continues from it unchanged.
+ *   Lp           shared rows: a multiple of 32 (the attention kernel's 32-row waves; the caller rounds the split down), >= 32
+ *   prefix:      d_ids / d_vis_slot int32 [U, Lp] (d_vis_slot: rows of d_merged, the U media's merged tokens), d_cos / d_sin fp32 [U*Lp, 64]
+ *   suffix:      d_ids / d_vis_slot int32 [B, Ls] (rows Lp .. Lp + Ls - 1 of each sample; d_vis_slot: rows of this call's d_merged), Ls >= 8
+ *                d_seq_len int32 [B] whole-sequence lengths (Lp < seq_len <= Lp + Ls), d_last_row int32 [B] = b*Ls + seq_len[b] - 1 - Lp,
+ *                d_cos / d_sin fp32 [B*Ls, 64] (the whole sequences' table rows), d_media_idx int32 [B] in [0, U) (outside: zero prefix rows)
+ * Invalid sizes (Lp not a multiple of 32, Ls < 8, Lp + Ls > VQS_QWEN_MAX_CACHE_POSITIONS) return VQS_ERR_INVALID before any launch; the
+ * *_bytes queries return 0 for them. */
+size_t vqs_qwen_prefix_kv_bytes(const vqs_qwen_handle* h, int32_t U, int32_t Lp);
+size_t vqs_qwen_prefix_workspace_bytes(const vqs_qwen_handle* h, int32_t U, int32_t Lp);
+int vqs_qwen_prefix(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const float* d_cos, const float* d_sin,
+                    int32_t U, int32_t Lp, void* d_pkv, size_t pkv_bytes, void* d_ws, size_t ws_bytes, void* stream);
+size_t vqs_qwen_suffix_workspace_bytes(const vqs_qwen_handle* h, int32_t B, int32_t Lp, int32_t Ls);
+int vqs_qwen_score_suffix(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                          const int32_t* d_last_row, const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int32_t B, int32_t Lp,
+                          int32_t Ls, const void* d_pkv, int32_t U, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* stream);
+int vqs_qwen_prefill_suffix(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                            const int32_t* d_last_row, const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int32_t B, int32_t Lp,
+                            int32_t Ls, const void* d_pkv, int32_t U, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv,
+                            size_t kv_bytes, int32_t Lmax, void* stream);
+
 /* Test hook (not part of the drop-in boundary): register a caller-owned device buffer for a named intermediate of the NEXT passes;
  * when a pass produces it, it is copied there on the pass's stream.  Names: vis.pre, vis.<i>.{h,xn0,q0,k0,q,k,v,attn,d_attn,xn1,ff,d_mlp},
  * vis.{h_out,xnm,mid,merged_w}; txt.emb, txt.<i>.{h,xn0,q0,k0,q,k,v,attn,d_attn,xn1,ff,d_mlp}, txt.{h_out,xnf}; of vqs_qwen_decode:

@@ -424,6 +424,221 @@ __global__ void __launch_bounds__(256) attn_fwd_hd_kernel(const AttnParams p) {
 #undef HD_PACK2
 }
 
+// =====================================================================================================
+// attn_suffix_hd_kernel<F16> -- the causal attn_fwd_hd_kernel<128, true, F16> for the query rows [q0, S) of each sample only (the
+// shared-prompt-prefix path of the Qwen2.5-VL row: the rows of a prompt prefix that all questions about one medium share were computed
+// once, include/vqs_qwen.h vqs_qwen_score_suffix).  Q and the output are compact (row q0 + r at row r); K / V are the whole sequence.
+// Bitwise the full kernel's rows: the same 64-key tiles in the same order, the same operand maps, the same online-softmax code.  What
+// couples rows in that code is the wave-uniform deferred rescale (__any over a wave's 32 query rows), so q0 must be a multiple of 32:
+// then every wave holds exactly the rows (and the clamped rows past S) of one wave of the full kernel.  The two kernels group waves
+// into 128-row blocks differently, so a wave may walk more or fewer tiles past its last row than in the full kernel -- those tiles are
+// masked for every one of its lanes (keys > qrow or >= key_len), and a fully masked tile is an exact no-op there: its max never passes
+// m_run + RESCALE_THR (tile 0 holds key 0 for every lane), and p = exp2(NEG_BIG * c - m_run) = 0 adds zero products.
+// =====================================================================================================
+template <bool F16 = false>
+__global__ void __launch_bounds__(256) attn_suffix_hd_kernel(const AttnSuffixParams p) {
+#define HD_MFMA(a, b, c) (F16 ? __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0) \
+                              : __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0))
+#define HD_PACK2(a, b) (F16 ? a_pack2h(a, b) : a_pack2(a, b))
+    constexpr int HD = 128;
+    constexpr int KS = HD / 16;
+    constexpr int DF = HD / 32;
+    constexpr int ROWB = HD * 2;
+    constexpr int KBYTES = KT * ROWB;
+    constexpr int STB = 2 * KBYTES;
+    constexpr int RPP = 1024 / ROWB;
+    constexpr int KPW = KT / RPP / 4;
+    constexpr int NDB = HD / 16;
+    constexpr int VPW = 2 * NDB / 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)A_LDS_PTR(smem));
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hh = lane >> 5;
+    const int S = p.S, q0 = p.q0;
+    const int nqb = (S - q0 + 127) >> 7;
+    const int slot = blockIdx.x >> 3;
+    const int qb = slot % nqb;
+    const int g = (slot / nqb) * 8 + (blockIdx.x & 7);
+    if (g >= p.B * p.H) return;
+    const int b = g / p.H, h = g - b * p.H;
+    const int Hkv = p.Hkv;
+    const int hk = h / (p.H / Hkv);
+    const bf16_t* Q = p.q + ((size_t)b * p.H + h) * p.Sq * HD;
+    const bf16_t* K = p.k + ((size_t)b * Hkv + hk) * S * HD;
+    const bf16_t* V = p.v + ((size_t)b * Hkv + hk) * S * HD;
+    const int klen = min(p.key_len[b], S);
+    const int r0 = q0 + qb * 128;                   // first query row of this block
+    int ntiles = (klen + KT - 1) / KT;
+    ntiles = min(ntiles, (min(r0 + 127, S - 1) >> 6) + 1);
+
+    constexpr float LOG2E = 1.4426950408889634f;
+    const float sl2 = p.scale * LOG2E;
+    const int qrow = r0 + wv * 32 + (lane & 31);
+    const int qrow_c = min(qrow, S - 1);
+    uint4 qf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+        qf[ks] = *reinterpret_cast<const uint4*>(Q + (size_t)(qrow_c - q0) * HD + 16 * ks + 8 * hh);
+
+    const a_v4i rsK = a_make_rsrc(K), rsV = a_make_rsrc(V);
+    constexpr int CPR = ROWB / 16;
+    int k_row[KPW], v_row[VPW];
+    uint32_t k_col[KPW], v_col[VPW], v_dst[VPW];
+#pragma unroll
+    for (int j = 0; j < KPW; ++j) {
+        const int r = RPP * (wv + 4 * j) + lane / CPR;
+        k_row[j] = r;
+        k_col[j] = (uint32_t)(((lane % CPR) ^ (r & 15)) << 4);
+    }
+#pragma unroll
+    for (int j = 0; j < VPW; ++j) {
+        const int db = wv + 4 * (j >> 1), kh = j & 1;
+        v_row[j] = 32 * kh + 4 * (((lane >> 3) - (db & 1)) & 7) + ((lane >> 1) & 3);
+        v_col[j] = (uint32_t)((16 * db + 8 * (lane & 1)) * 2);
+        v_dst[j] = (uint32_t)(KBYTES + (kh * NDB + db) * 1024);
+    }
+    auto stage = [&](int kt, int st) {
+        const int kb = kt * KT;
+        const uint32_t sb = lds_base + st * STB;
+#pragma unroll
+        for (int j = 0; j < KPW; ++j)
+            a_bglds16(rsK, (uint32_t)min(kb + k_row[j], S - 1) * (uint32_t)ROWB + k_col[j], sb + (wv + 4 * j) * 1024);
+#pragma unroll
+        for (int j = 0; j < VPW; ++j)
+            a_bglds16(rsV, (uint32_t)min(kb + v_row[j], S - 1) * (uint32_t)ROWB + v_col[j], sb + v_dst[j]);
+    };
+
+    f32x16 o[DF];
+#pragma unroll
+    for (int df = 0; df < DF; ++df)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[df][r] = 0.0f;
+    f32x16 osum;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) osum[r] = 0.0f;
+    float m_run = NEG_BIG;
+    uint4 ones;
+    ones.x = ones.y = ones.z = ones.w = F16 ? 0x3c003c00u : 0x3f803f80u;
+
+    const int swr = lane & 15;
+    const int k_rd = (lane & 31) * ROWB;
+    const int dbl = (lane >> 4) & 1, tq = lane & 15;
+    int v_rd[4];
+#pragma unroll
+    for (int xi = 0; xi < 4; ++xi)
+        v_rd[xi] = KBYTES + dbl * 1024 + (((2 * xi + hh + dbl) & 7) << 7) + (tq >> 2) * 32 + (tq & 3) * 8;
+
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks].x), "+v"(qf[ks].y), "+v"(qf[ks].z), "+v"(qf[ks].w));
+    if (ntiles > 0) stage(0, 0);
+    for (int kt = 0; kt < ntiles; ++kt) {
+        const int st = kt & 1;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (kt + 1 < ntiles) stage(kt + 1, st ^ 1);
+        const char* k_lds = smem + st * STB;
+
+        f32x16 s[2];
+#pragma unroll
+        for (int kf = 0; kf < 2; ++kf)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[kf][r] = 0.0f;
+#pragma unroll
+        for (int k4 = 0; k4 < KS; k4 += 4) {
+            uint4 kfr[4][2];
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int kf = 0; kf < 2; ++kf)
+                    kfr[ks][kf] = *reinterpret_cast<const uint4*>(k_lds + kf * 32 * ROWB + k_rd + (((2 * (k4 + ks) + hh) ^ swr) << 4));
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int kf = 0; kf < 2; ++kf)
+                    s[kf] = HD_MFMA(kfr[ks][kf], qf[k4 + ks], s[kf]);
+        }
+
+        const int kb = kt * KT;
+        if (kb + KT > klen || kb + KT - 1 > r0 + wv * 32) {      // wave-uniform
+#pragma unroll
+            for (int kf = 0; kf < 2; ++kf)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = kb + kf * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                    if (key >= klen || key > qrow) s[kf][r] = NEG_BIG;
+                }
+        }
+#define VQS_SV(i) s[(i) >> 4][(i) & 15]
+        float mx = a_max3(VQS_SV(0), VQS_SV(1), VQS_SV(2));
+#pragma unroll
+        for (int i = 3; i < 31; i += 2) mx = a_max3(mx, VQS_SV(i), VQS_SV(i + 1));
+        mx = fmaxf(mx, VQS_SV(31));
+#undef VQS_SV
+        mx = a_max_xhalf(mx);
+        mx *= sl2;
+        if (__any(mx > m_run + RESCALE_THR)) {
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+            m_run = m_new;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+#pragma unroll
+                for (int df = 0; df < DF; ++df) o[df][r] *= alpha;
+                osum[r] *= alpha;
+            }
+        }
+        const float neg_m = -m_run;
+#pragma unroll
+        for (int kf = 0; kf < 2; ++kf)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[kf][r] = __builtin_amdgcn_exp2f(fmaf(s[kf][r], sl2, neg_m));
+
+#pragma unroll
+        for (int kf = 0; kf < 2; ++kf)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                uint4 pb;
+                pb.x = HD_PACK2(s[kf][8 * t + 0], s[kf][8 * t + 1]);
+                pb.y = HD_PACK2(s[kf][8 * t + 2], s[kf][8 * t + 3]);
+                pb.z = HD_PACK2(s[kf][8 * t + 4], s[kf][8 * t + 5]);
+                pb.w = HD_PACK2(s[kf][8 * t + 6], s[kf][8 * t + 7]);
+                osum = HD_MFMA(ones, pb, osum);
+#pragma unroll
+                for (int df = 0; df < DF; ++df) {
+                    const char* vp = k_lds + (kf * NDB + 2 * df) * 1024;
+                    const a_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                        (__attribute__((address_space(3))) a_v4s*)A_LDS_PTR(vp + v_rd[2 * t + 0]));
+                    const a_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                        (__attribute__((address_space(3))) a_v4s*)A_LDS_PTR(vp + v_rd[2 * t + 1]));
+                    const uint2 lo2 = __builtin_bit_cast(uint2, lo), hi2 = __builtin_bit_cast(uint2, hi);
+                    uint4 va;
+                    va.x = lo2.x; va.y = lo2.y; va.z = hi2.x; va.w = hi2.y;
+                    o[df] = HD_MFMA(va, pb, o[df]);
+                }
+            }
+    }
+
+    const float l_tot = osum[0];
+    const float inv = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
+    if (qrow < S && qrow - q0 < p.Sq) {
+        bf16_t* orow = p.out + ((size_t)b * p.Sq + (qrow - q0)) * ((size_t)p.H * HD) + h * HD;
+#pragma unroll
+        for (int df = 0; df < DF; ++df)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                uint2 v;
+                v.x = HD_PACK2(o[df][4 * gq + 0] * inv, o[df][4 * gq + 1] * inv);
+                v.y = HD_PACK2(o[df][4 * gq + 2] * inv, o[df][4 * gq + 3] * inv);
+                *reinterpret_cast<uint2*>(orow + df * 32 + 8 * gq + 4 * hh) = v;
+            }
+    }
+#undef HD_MFMA
+#undef HD_PACK2
+}
+
 static constexpr int attn_variant() { return 1; }        // the shipped library holds the LDS-DMA kernel only
 static constexpr size_t attn_lds_pad() { return 0; }
 
@@ -463,6 +678,17 @@ hipError_t launch_attention(const AttnParams& p, hipStream_t stream) {
                             : launch_attn_t(attn_fwd_dma_f16_kernel<false>, p, lds, stream);
     return p.bias_table ? launch_attn_t(attn_fwd_dma_kernel<true>, p, lds, stream)
                         : launch_attn_t(attn_fwd_dma_kernel<false>, p, lds, stream);
+}
+
+hipError_t launch_attention_suffix(const AttnSuffixParams& p, hipStream_t stream) {
+    if (p.B <= 0 || p.H <= 0 || p.Hkv <= 0 || (p.H % p.Hkv) != 0 || !p.key_len) return hipErrorInvalidValue;
+    if (p.q0 < 0 || (p.q0 % 32) != 0 || p.q0 >= p.S || p.Sq < p.S - p.q0) return hipErrorInvalidValue;
+    const size_t lds = 2 * 2 * (size_t)KT * 128 * 2;            // as attn_fwd_hd_kernel: two stages of K + V tiles
+    const int nqb = (p.S - p.q0 + 127) / 128, G = p.B * p.H;
+    const dim3 grid(((G + 7) / 8) * 8 * nqb), block(256);
+    if (p.f16) hipLaunchKernelGGL(attn_suffix_hd_kernel<true>, grid, block, lds, stream, p);
+    else hipLaunchKernelGGL(attn_suffix_hd_kernel<false>, grid, block, lds, stream, p);
+    return hipGetLastError();
 }
 
 // Dynamic LDS request of the self-attention kernel launch_attention() picks for (S, bias, hd): what the occupancy of the

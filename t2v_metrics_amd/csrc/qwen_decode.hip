@@ -420,6 +420,42 @@ hipError_t launch_f16_to_bf16_rows(const bf16_t* src, bf16_t* dst, int rows, lon
     return hipGetLastError();
 }
 
+// Shared prompt prefix: one layer's K (blockIdx.z = 0) or V (1) slab [B, Hkv, Lp + Ls, 128] of every sample, rows [0, Lp) gathered from
+// its medium's prefix rows, rows [Lp, Lp + Ls) from its own suffix rows.  blockIdx.y = one (sample, kv head) slab; one thread per 16-byte
+// chunk (16 per 256-byte row), 32-bit index arithmetic within the slab.
+__global__ void __launch_bounds__(256) qwen_kv_assemble_kernel(const uint4* __restrict__ pk, const uint4* __restrict__ pv, const uint4* __restrict__ sk,
+                                                               const uint4* __restrict__ sv, const int* __restrict__ media_idx, uint4* __restrict__ dk,
+                                                               uint4* __restrict__ dv, int U, int Hkv, int Lp, int Ls) {
+    const bool is_v = blockIdx.z != 0;
+    const int bh = blockIdx.y, b = bh / Hkv, hh = bh - b * Hkv;
+    const int L = Lp + Ls, n = L * 16;
+    const int u = media_idx[b];
+    const uint4* pre = (u >= 0 && u < U) ? (is_v ? pv : pk) + ((size_t)u * Hkv + hh) * Lp * 16 : nullptr;
+    const uint4* suf = (is_v ? sv : sk) + (size_t)bh * Ls * 16;
+    uint4* dst = (is_v ? dv : dk) + (size_t)bh * L * 16;
+    const int lp16 = Lp * 16;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        uint4 val = make_uint4(0u, 0u, 0u, 0u);
+        if (i < lp16) {
+            if (pre) val = pre[i];
+        } else {
+            val = suf[i - lp16];
+        }
+        dst[i] = val;
+    }
+}
+hipError_t launch_qwen_kv_assemble(const bf16_t* pk, const bf16_t* pv, const bf16_t* sk, const bf16_t* sv, const int* media_idx, bf16_t* dk,
+                                   bf16_t* dv, int B, int U, int Hkv, int Lp, int Ls, hipStream_t s) {
+    if (B <= 0 || U <= 0 || Hkv <= 0 || Lp < 0 || Ls <= 0 || (long long)B * Hkv > 65535 || (long long)(Lp + Ls) * 16 > (1LL << 30))
+        return hipErrorInvalidValue;
+    const int n = (Lp + Ls) * 16;
+    const unsigned bx = (unsigned)std::min((n + 255) / 256, 64);
+    hipLaunchKernelGGL(qwen_kv_assemble_kernel, dim3(bx, (unsigned)(B * Hkv), 2), dim3(256), 0, s, reinterpret_cast<const uint4*>(pk),
+                       reinterpret_cast<const uint4*>(pv), reinterpret_cast<const uint4*>(sk), reinterpret_cast<const uint4*>(sv), media_idx,
+                       reinterpret_cast<uint4*>(dk), reinterpret_cast<uint4*>(dv), U, Hkv, Lp, Ls);
+    return hipGetLastError();
+}
+
 // The precise tail's rotary embedding: q columns of the fp32 q|k|v row of each sample's LAST position, rotated by that position's table
 // (rope_qk_kernel's arithmetic -- x[i] c[i] - x[i + half] s[i], x[i + half] c[i] + x[i] s[i] -- without its bf16 rounding), -> fp32 [B, Hq * hd].
 // Block (query head, sample), 64 threads; table row = row[b] (the sample's last valid position in the [B * L, half] tables).

@@ -1566,6 +1566,31 @@ int vqs_debug_attention_f16(const void* q, const void* k, const void* v, void* o
     return vqs::launch_attention(a, (hipStream_t)stream) == hipSuccess ? VQS_OK : VQS_ERR_HIP;
 }
 
+static int debug_rc(hipError_t e) { return e == hipSuccess ? VQS_OK : e == hipErrorInvalidValue ? VQS_ERR_INVALID : VQS_ERR_HIP; }
+
+int vqs_debug_qwen_attention(const void* q, const void* k, const void* v, void* out, const int32_t* key_len, int32_t B, int32_t H, int32_t Hkv,
+                             int32_t S, float scale, int32_t f16, void* stream) {
+    if (!q || !k || !v || !out || !key_len) return VQS_ERR_INVALID;
+    vqs::AttnParams a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, nullptr, key_len, B, H, S, scale};
+    a.hd = 128; a.Hkv = Hkv; a.causal = 1; a.f16 = f16 ? 1 : 0;
+    return debug_rc(vqs::launch_attention(a, (hipStream_t)stream));
+}
+
+int vqs_debug_qwen_attention_suffix(const void* q, const void* k, const void* v, void* out, const int32_t* key_len, int32_t B, int32_t H,
+                                    int32_t Hkv, int32_t S, int32_t Sq, int32_t q0, float scale, int32_t f16, void* stream) {
+    if (!q || !k || !v || !out || !key_len) return VQS_ERR_INVALID;
+    vqs::AttnSuffixParams a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, key_len, B, H, Hkv, S, Sq, q0, scale};
+    a.f16 = f16 ? 1 : 0;
+    return debug_rc(vqs::launch_attention_suffix(a, (hipStream_t)stream));
+}
+
+int vqs_debug_qwen_kv_assemble(const void* pk, const void* pv, const void* sk, const void* sv, const int32_t* media_idx, void* dk, void* dv,
+                               int32_t B, int32_t U, int32_t Hkv, int32_t Lp, int32_t Ls, void* stream) {
+    if (!pk || !pv || !sk || !sv || !media_idx || !dk || !dv) return VQS_ERR_INVALID;
+    return debug_rc(vqs::launch_qwen_kv_assemble((const bf16_t*)pk, (const bf16_t*)pv, (const bf16_t*)sk, (const bf16_t*)sv, media_idx, (bf16_t*)dk,
+                                                 (bf16_t*)dv, B, U, Hkv, Lp, Ls, (hipStream_t)stream));
+}
+
 int vqs_debug_norm16(int32_t kind, float* x, const void* delta, const void* delta2, int32_t store_x, const void* w, const void* b,
                      void* out, int32_t M, int32_t D, float eps, int32_t types, void* stream) {
     if (!x || !w || !out || (kind == 1 && !b) || (kind != 0 && kind != 1)) return VQS_ERR_INVALID;

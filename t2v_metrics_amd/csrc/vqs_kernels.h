@@ -326,4 +326,25 @@ hipError_t launch_u8_to_norm_bf16(const unsigned char* in, bf16_t* out, int N, i
                                   const float* std3, hipStream_t s);
 hipError_t launch_interleave_gate(const bf16_t* wi0, const bf16_t* wi1, bf16_t* dst, int F, int D, hipStream_t s);
 
+// ---- shared-prompt-prefix passes of the Qwen2.5-VL row (include/vqs_qwen.h vqs_qwen_prefix / vqs_qwen_score_suffix)
+// Suffix attention (attn.hip): query rows [q0, S) of every sample -- q compact [B, H, Sq, 128] (row r of it = position q0 + r,
+// Sq >= S - q0), k / v full slabs [B, Hkv, S, 128], out compact [B*Sq, H*128] -- causal over keys [0, qrow] and below key_len[b].
+// Every row is bitwise the row attn_fwd_hd_kernel computes over the whole sequence when q0 is a multiple of 32.
+struct AttnSuffixParams {
+    const bf16_t* q;
+    const bf16_t* k;
+    const bf16_t* v;
+    bf16_t* out;
+    const int* key_len;       // [B]
+    int B, H, Hkv, S, Sq, q0;
+    float scale;
+    int f16 = 0;              // q / k / v / out IEEE fp16 (the range-safe fp16 forms) instead of bf16
+};
+hipError_t launch_attention_suffix(const AttnSuffixParams& p, hipStream_t stream);
+// K and V slabs of one layer (qwen_decode.hip): dst [B, Hkv, Lp + Ls, 128] rows [0, Lp) = prefix store rows of medium media_idx[b]
+// ([U, Hkv, Lp, 128]), rows [Lp, Lp + Ls) = the sample's own suffix rows ([B, Hkv, Ls, 128]); 16-bit elements copied as they are.
+// A media_idx outside [0, U) yields zero prefix rows.
+hipError_t launch_qwen_kv_assemble(const bf16_t* pk, const bf16_t* pv, const bf16_t* sk, const bf16_t* sv, const int* media_idx, bf16_t* dk,
+                                   bf16_t* dv, int B, int U, int Hkv, int Lp, int Ls, hipStream_t s);
+
 }  // namespace vqs

@@ -1331,3 +1331,225 @@ int vqs_qwen_decode(vqs_qwen_handle* h, const int32_t* d_ids, const int32_t* d_l
 }
 
 }  // extern "C"
+
+namespace {
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Shared prompt prefix (include/vqs_qwen.h vqs_qwen_prefix / vqs_qwen_score_suffix / vqs_qwen_prefill_suffix).  The first Lp rows of
+// every prompt about one medium are the same tokens at the same positions, and the language model is causal: their K / V in every layer
+// do not depend on the question.  The prefix pass runs score_impl's layer sequence over U prefixes and leaves each layer's K (rotated) and
+// V in the prefix store, in the tensors the attention reads (bf16, or fp16 behind the layer's q|k|v scale).  The suffix pass runs the
+// same sequence over the suffix rows only; per layer, launch_qwen_kv_assemble builds the [B, Hkv, Lp + Ls, 128] slabs score_impl has in
+// w.k / w.v (prefix rows from the store, suffix rows from the q|k|v launch), and the precise tail, the cache copy and the decode step read
+// them unchanged.  Every launch is row-independent (GEMM forms are a function of the weight's shape, never of M; norms, embedding and rope
+// are per row) except attention, whose rows couple through the wave-uniform deferred rescale: Lp is a multiple of 32 so that the prefix
+// pass (attn_fwd_hd_kernel over Lp rows) and the suffix pass (attn_suffix_hd_kernel over rows [Lp, L)) hold the same 32-row waves as
+// the full kernel over L rows.  Result: bitwise the logits and cache of vqs_qwen_score / vqs_qwen_prefill over the whole prompts.
+// ---------------------------------------------------------------------------------------------------------------------------------
+inline size_t prefix_slab(const vqs_qwen_handle* h, int U, int Lp) { return (size_t)U * h->c.t_kv_heads * (size_t)Lp * HDP; }
+
+struct SharedWs {
+    TxtWs w;
+    bf16_t *sk = nullptr, *sv = nullptr;   // suffix pass: the suffix rows' own K / V [B, Hkv, Ls, 128]
+    int* key_len = nullptr;                // prefix pass: Lp per prefix
+    size_t total = 0;
+};
+SharedWs carve_shared(const vqs_qwen_handle* h, char* base, int R, int Lp, int Ls, bool suffix) {
+    SharedWs s;
+    s.w = carve_text(h, base, R, suffix ? Lp + Ls : Lp);
+    Carver cv{base};
+    cv.off = s.w.total;
+    if (suffix) {
+        s.sk = cv.take<bf16_t>((size_t)R * Ls * h->t_ikv);
+        s.sv = cv.take<bf16_t>((size_t)R * Ls * h->t_ikv);
+    } else {
+        s.key_len = cv.take<int>((size_t)R);
+    }
+    s.total = align_up(cv.off);
+    return s;
+}
+bool prefix_shape_ok(int U, int Lp) { return U > 0 && Lp >= 32 && (Lp % 32) == 0 && Lp <= VQS_QWEN_MAX_CACHE_POSITIONS; }
+bool suffix_shape_ok(int B, int Lp, int Ls) {
+    return B > 0 && Lp >= 32 && (Lp % 32) == 0 && Ls >= 8 && (int64_t)Lp + Ls <= VQS_QWEN_MAX_CACHE_POSITIONS;
+}
+
+// suffix == false: the prefix pass (R = U prompt prefixes of Lp rows); true: the suffix pass (R = B suffixes of Ls rows behind the prefixes
+// of media d_media_idx), d_kv != nullptr also fills the decode cache
+int shared_impl(vqs_qwen_handle* h, bool suffix, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                const int32_t* d_last_row, const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int R, int U, int Lp, int Ls,
+                const void* d_pkv, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv, int Lmax, hipStream_t st) {
+    const vqs_qwen_config& c = h->c;
+    const int S = suffix ? Ls : Lp;                // rows per sample of this pass
+    const int L = suffix ? Lp + Ls : Lp;           // keys per sample of its attention
+    const SharedWs sw = carve_shared(h, (char*)d_ws, R, Lp, Ls, suffix);
+    if (ws_bytes < sw.total) return qfail(h, VQS_ERR_WORKSPACE, "shared prefix: workspace too small");
+    const TxtWs& w = sw.w;
+    const int TH = c.t_hidden, M = R * S, IKV = h->t_ikv, XLD = h->t_xld;
+    const float scale = 1.0f / sqrtf((float)h->t_hd);
+    const bool F = h->fp16_active != 0;
+    QW(embed, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * TH);
+    QHIP(h, vqs::launch_qwen_embed(d_ids, d_vis_slot, embed, (const bf16_t*)d_merged, w.hidden, M, TH, c.t_vocab, st, F, F ? 1.0f / h->m_out.sigma : 1.0f), "embed + splice");
+    QHIP(h, hipMemsetAsync(w.ff, 0, (size_t)M * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
+    const bool tail = suffix && h->tail_precise != 0 && (c.t_vocab % 4) == 0 && (c.t_hidden % 4) == 0;
+    if (tail) QHIP(h, vqs::launch_gather_rows_f32(w.hidden, d_last_row, w.t_h, R, TH, TH, st), "tail embed rows");
+    if (!suffix) QHIP(h, hipMemsetD32Async((hipDeviceptr_t)sw.key_len, Lp, (size_t)R, st), "prefix key lengths");
+    const vqs_qwen_handle::LayerSites one{};
+    const bool rope_in_gemm = F && h->rope_fused != 0 && h->t_hd == HDP;
+    auto norm = [&](const bf16_t* d, const bf16_t* g, const bf16_t* d2, bool store, float sd1, float sd2, float so, bool out_bf16, const char* what) -> int {
+        if (F) QHIP(h, vqs::launch_rmsnorm_f16s(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD, 1.0f / sd1, 1.0f / sd2, so, out_bf16), what);
+        else QHIP(h, vqs::launch_rmsnorm(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD), what);
+        return VQS_OK;
+    };
+    const bf16_t* pend = nullptr;
+    const bf16_t* pend_attn = nullptr;
+    float s_pend = 1.0f, s_pend_attn = 1.0f;
+    for (int i = 0; i < c.t_layers; ++i) {
+        const std::string p = "model.language_model.layers." + std::to_string(i) + ".";
+        QW(ln1, p + "input_layernorm.weight", TH);
+        QW(ln2, p + "post_attention_layernorm.weight", TH);
+        const vqs_qwen_handle::LayerSites& sc = F ? h->t_sc[i] : one;
+        bf16_t* pk = (bf16_t*)d_pkv + (size_t)(2 * i) * prefix_slab(h, U, Lp);
+        bf16_t* pv = pk + prefix_slab(h, U, Lp);
+        bf16_t* kout = suffix ? sw.sk : pk;
+        bf16_t* vout = suffix ? sw.sv : pv;
+        QRUN(norm(pend_attn ? pend_attn : pend, ln1, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, sc.x0.sigma, false, "input_layernorm"));
+        {
+            GCall g{w.xn, F ? h->t_qkv_h[i] : h->t_qkv_w[i], nullptr};
+            g.bias = h->t_qkv_b[i];
+            g.M = M; g.N = h->t_iq + 2 * IKV; g.K = TH; g.lda = XLD; g.ldw = TH; g.epi = vqs::EPI_HEADS;
+            g.S = S; g.H = c.t_heads; g.inner = h->t_iq; g.hd = HDP; g.inner_kv = IKV; g.Hkv = c.t_kv_heads;
+            g.heads[0] = w.q; g.heads[1] = kout; g.heads[2] = vout;
+            if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x0.sigma; g.out_scale = sc.qkv.sigma; }
+            if (rope_in_gemm) { g.rope_cos = d_cos; g.rope_sin = d_sin; }
+            QRUN(qgemm(h, g, st, "qkv"));
+        }
+        if (!rope_in_gemm) QHIP(h, vqs::launch_rope_qk(w.q, kout, d_cos, d_sin, R, c.t_heads, c.t_kv_heads, S, HDP, h->t_hd / 2, st, F), "rope");
+        if (!suffix && i == c.t_layers - 1) break;     // the last layer's K / V are all the suffix pass reads of the prefix
+        const float a_scale = scale / (sc.qkv.sigma * sc.qkv.sigma);
+        if (suffix) {
+            QHIP(h, vqs::launch_qwen_kv_assemble(pk, pv, sw.sk, sw.sv, d_media_idx, w.k, w.v, R, U, c.t_kv_heads, Lp, Ls, st), "assemble K / V slabs");
+            if (d_kv) {   // as score_impl: rows [b, head, 0 .. L) of the cache slabs, bf16 in true units
+                bf16_t* kc = (bf16_t*)d_kv + (size_t)(2 * i) * kv_slab(h, R, Lmax);
+                bf16_t* vc = kc + kv_slab(h, R, Lmax);
+                const size_t wb = (size_t)L * HDP * sizeof(bf16_t), pb = (size_t)Lmax * HDP * sizeof(bf16_t), nr = (size_t)R * c.t_kv_heads;
+                if (F) {
+                    if (nr > 65535) return qfail(h, VQS_ERR_INVALID, "prefill: B * kv_heads exceeds 65535");
+                    QHIP(h, vqs::launch_f16_to_bf16_rows(w.k, kc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep K");
+                    QHIP(h, vqs::launch_f16_to_bf16_rows(w.v, vc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep V");
+                } else {
+                    QHIP(h, hipMemcpy2DAsync(kc, pb, w.k, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep K");
+                    QHIP(h, hipMemcpy2DAsync(vc, pb, w.v, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep V");
+                }
+            }
+            vqs::AttnSuffixParams a{w.q, w.k, w.v, w.attn, d_seq_len, R, c.t_heads, c.t_kv_heads, L, Ls, Lp, a_scale};
+            a.f16 = F ? 1 : 0;
+            QHIP(h, vqs::launch_attention_suffix(a, st), "suffix attention");
+        } else {
+            vqs::AttnParams a{w.q, pk, pv, w.attn, nullptr, sw.key_len, R, c.t_heads, Lp, a_scale};
+            a.hd = HDP; a.Hkv = c.t_kv_heads; a.causal = 1; a.f16 = F ? 1 : 0;
+            QHIP(h, vqs::launch_attention(a, st), "prefix attention");
+        }
+        if (tail) QRUN(tail_layer(h, w, i, ln1, ln2, d_seq_len, d_last_row, d_cos, d_sin, R, L, i == 0, st, F, sc.qkv.sigma));
+        {
+            GCall g{w.attn, F ? h->t_o_h[i] : h->t_o_w[i], w.delta};
+            g.M = M; g.N = TH; g.K = h->t_iq; g.lda = h->t_iq; g.ldw = h->t_iq; g.ldc = TH; g.epi = vqs::EPI_BF16;
+            if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.qkv.sigma; g.out_scale = sc.dattn.sigma; }
+            QRUN(qgemm(h, g, st, "o_proj"));
+        }
+        QRUN(norm(w.delta, ln2, nullptr, false, sc.dattn.sigma, 1.0f, sc.x1.sigma, false, "post_attention_layernorm"));
+        pend_attn = w.delta; s_pend_attn = sc.dattn.sigma;
+        {
+            GCall g{w.xn, F ? h->t_gu_h[i] : h->t_gu_w[i], w.ff};
+            g.M = M; g.N = 2 * h->t_mlp_p; g.K = TH; g.lda = XLD; g.ldw = XLD; g.ldc = h->t_ffld; g.epi = vqs::EPI_GATED; g.gate_act = 1;
+            if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x1.sigma; g.out_scale = sc.act.sigma; }
+            QRUN(qgemm(h, g, st, "gate|up"));
+        }
+        {
+            GCall g{w.ff, F ? h->t_down_h[i] : h->t_down_w[i], w.delta2};
+            g.M = M; g.N = TH; g.K = h->t_ffld; g.lda = h->t_ffld; g.ldw = h->t_ffld; g.ldc = TH; g.epi = vqs::EPI_BF16;
+            if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.act.sigma; g.out_scale = sc.dmlp.sigma; }
+            QRUN(qgemm(h, g, st, "down_proj"));
+            pend = w.delta2; s_pend = sc.dmlp.sigma;
+        }
+    }
+    if (!suffix) return VQS_OK;
+    QW(fin, "model.language_model.norm.weight", TH);
+    QW(head, "lm_head.weight", (int64_t)c.t_vocab * TH);
+    QRUN(norm(pend_attn ? pend_attn : pend, fin, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, 1.0f, true, "final norm"));
+    if (tail) return tail_head(h, w, fin, head, d_logits, R, st);
+    QHIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, d_last_row, w.last, R, TH, XLD, TH, st), "last positions");
+    {
+        GCall g{w.last, head, d_logits};
+        g.M = R; g.N = c.t_vocab; g.K = TH; g.lda = TH; g.ldw = TH; g.ldc = c.t_vocab; g.epi = vqs::EPI_F32;
+        QRUN(qgemm(h, g, st, "lm_head"));
+    }
+    return VQS_OK;
+}
+
+int suffix_entry(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                 const int32_t* d_last_row, const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int32_t B, int32_t Lp, int32_t Ls,
+                 const void* d_pkv, int32_t U, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv, size_t kv_bytes,
+                 int32_t Lmax, bool cached, void* stream) {
+    if (!h) return VQS_ERR_INVALID;
+    // sizes first: an invalid shape is refused whatever else is wrong with the call
+    if (!suffix_shape_ok(B, Lp, Ls) || !prefix_shape_ok(U, Lp))
+        return qfail(h, VQS_ERR_INVALID, "score_suffix: need B, U > 0, Lp a multiple of 32 (>= 32), Ls >= 8, Lp + Ls <= " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS));
+    if (cached && Lmax > VQS_QWEN_MAX_CACHE_POSITIONS)
+        return qfail(h, VQS_ERR_INVALID, "prefill_suffix: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
+    if (!h->bound) return qfail(h, VQS_ERR_STATE, "score_suffix: weights not bound");
+    if (!d_merged || !d_ids || !d_vis_slot || !d_seq_len || !d_last_row || !d_cos || !d_sin || !d_media_idx || !d_pkv || !d_logits || !d_ws)
+        return qfail(h, VQS_ERR_INVALID, "score_suffix: null argument");
+    if (pkv_bytes < vqs_qwen_prefix_kv_bytes(h, U, Lp)) return qfail(h, VQS_ERR_WORKSPACE, "score_suffix: prefix store too small");
+    if (cached) {
+        if (!d_kv || Lmax < Lp + Ls || kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return qfail(h, VQS_ERR_WORKSPACE, "prefill_suffix: KV cache missing or too small");
+        if (h->fp16_active && (int64_t)B * h->c.t_kv_heads > 65535) return qfail(h, VQS_ERR_INVALID, "prefill_suffix: B * kv_heads exceeds 65535");
+    }
+    return shared_impl(h, true, d_merged, d_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, d_media_idx, B, U, Lp, Ls, d_pkv, pkv_bytes, d_logits,
+                       d_ws, ws_bytes, cached ? d_kv : nullptr, Lmax, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" {
+
+size_t vqs_qwen_prefix_kv_bytes(const vqs_qwen_handle* h, int32_t U, int32_t Lp) {
+    if (!h || !prefix_shape_ok(U, Lp)) return 0;
+    return (size_t)2 * h->c.t_layers * prefix_slab(h, U, Lp) * sizeof(bf16_t);
+}
+
+size_t vqs_qwen_prefix_workspace_bytes(const vqs_qwen_handle* h, int32_t U, int32_t Lp) {
+    if (!h || !prefix_shape_ok(U, Lp)) return 0;
+    return carve_shared(h, nullptr, U, Lp, 0, false).total;
+}
+
+size_t vqs_qwen_suffix_workspace_bytes(const vqs_qwen_handle* h, int32_t B, int32_t Lp, int32_t Ls) {
+    if (!h || !suffix_shape_ok(B, Lp, Ls)) return 0;
+    return carve_shared(h, nullptr, B, Lp, Ls, true).total;
+}
+
+int vqs_qwen_prefix(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const float* d_cos, const float* d_sin,
+                    int32_t U, int32_t Lp, void* d_pkv, size_t pkv_bytes, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!h) return VQS_ERR_INVALID;
+    if (!prefix_shape_ok(U, Lp))       // sizes first, as vqs_qwen_score_suffix
+        return qfail(h, VQS_ERR_INVALID, "prefix: need U > 0 and Lp a multiple of 32 in [32, " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + "]");
+    if (!h->bound) return qfail(h, VQS_ERR_STATE, "prefix: weights not bound");
+    if (!d_merged || !d_ids || !d_vis_slot || !d_cos || !d_sin || !d_pkv || !d_ws) return qfail(h, VQS_ERR_INVALID, "prefix: null argument");
+    if (pkv_bytes < vqs_qwen_prefix_kv_bytes(h, U, Lp)) return qfail(h, VQS_ERR_WORKSPACE, "prefix: prefix store too small");
+    return shared_impl(h, false, d_merged, d_ids, d_vis_slot, nullptr, nullptr, d_cos, d_sin, nullptr, U, U, Lp, 0, d_pkv, pkv_bytes, nullptr, d_ws,
+                       ws_bytes, nullptr, 0, (hipStream_t)stream);
+}
+
+int vqs_qwen_score_suffix(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                          const int32_t* d_last_row, const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int32_t B, int32_t Lp,
+                          int32_t Ls, const void* d_pkv, int32_t U, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* stream) {
+    return suffix_entry(h, d_merged, d_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, d_media_idx, B, Lp, Ls, d_pkv, U, pkv_bytes, d_logits, d_ws,
+                        ws_bytes, nullptr, 0, 0, false, stream);
+}
+
+int vqs_qwen_prefill_suffix(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                            const int32_t* d_last_row, const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int32_t B, int32_t Lp,
+                            int32_t Ls, const void* d_pkv, int32_t U, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv,
+                            size_t kv_bytes, int32_t Lmax, void* stream) {
+    return suffix_entry(h, d_merged, d_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, d_media_idx, B, Lp, Ls, d_pkv, U, pkv_bytes, d_logits, d_ws,
+                        ws_bytes, d_kv, kv_bytes, Lmax, true, stream);
+}
+
+}  // extern "C"

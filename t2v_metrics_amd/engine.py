@@ -74,6 +74,9 @@ _SIGNATURES = {
     "vqs_debug_tap": (_c_i32, [_c_vp, ctypes.c_char_p, _c_vp, ctypes.c_size_t]),
     "vqs_debug_tap_window": (_c_i32, [_c_vp, _c_i32, _c_i32]),
     "vqs_debug_attention_f16": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i32, _c_i32, _c_i32, ctypes.c_float, _c_vp]),
+    "vqs_debug_qwen_attention": (_c_i32, [_c_vp] * 5 + [_c_i32] * 4 + [ctypes.c_float, _c_i32, _c_vp]),
+    "vqs_debug_qwen_attention_suffix": (_c_i32, [_c_vp] * 5 + [_c_i32] * 6 + [ctypes.c_float, _c_i32, _c_vp]),
+    "vqs_debug_qwen_kv_assemble": (_c_i32, [_c_vp] * 7 + [_c_i32] * 5 + [_c_vp]),
     "vqs_debug_norm16": (_c_i32, [_c_i32, _c_vp, _c_vp, _c_vp, _c_i32, _c_vp, _c_vp, _c_vp, _c_i32, _c_i32, ctypes.c_float, _c_i32, _c_vp]),
     "vqs_debug_gemm_form": (_c_i32, [_c_i32] * 11),
     "vqs_debug_gemm_batched": (_c_i32, [_c_vp, _c_vp, _c_vp] + [_c_i32] * 8 + [_c_i64] * 4 + [_c_i32, _c_i32, _c_vp]),

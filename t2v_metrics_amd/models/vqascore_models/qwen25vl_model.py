@@ -126,10 +126,13 @@ class Qwen25VLModel(VQAScoreModel):
 
     def __init__(self, model_name='qwen2.5-vl-7b', device='cuda', cache_dir=HF_CACHE_DIR, checkpoint: Optional[str] = None,
                  weights=None, tokenizer=None, config: Optional[Qwen25VLConfig] = None, engine=None, max_batch: int = 32,
-                 seed: int = 0, num_workers: Optional[int] = None):
+                 seed: int = 0, num_workers: Optional[int] = None, share_prefix: bool = True):
         """weights: None -> ``checkpoint`` (local HF directory of safetensors); 'seeded' -> seeded random weights at the
         architecture; or a dict.  tokenizer: object with ``encode(text, add_special_tokens=False) -> List[int]`` that maps
-        the chat-template special tokens (HF protocol); None -> the checkpoint's tokenizer."""
+        the chat-template special tokens (HF protocol); None -> the checkpoint's tokenizer.  share_prefix: a batch in which a
+        medium has several questions runs its prompt prefix (chat header + vision run + <|vision_end|>) through the language
+        model once (QwenEngine.score_shared; bitwise the same scores); False = every pair runs its whole prompt."""
+        self.share_prefix = bool(share_prefix)
         assert config is not None or model_name in QWEN25_VL_MODELS, f"Model {model_name} not found in QWEN25_VL_MODELS"
         self._cfg = config if config is not None else get_qwen_config(QWEN25_VL_MODELS[model_name]['config'])
         self._weights_arg, self._tokenizer_arg, self._checkpoint, self._engine_arg = weights, tokenizer, checkpoint, engine
@@ -344,7 +347,7 @@ class Qwen25VLModel(VQAScoreModel):
                 # ---- greedy generation (HF generate, do_sample=False): ONE prefill that keeps the KV cache, then one cached
                 # position per further token; a sample stops at its first stop id, exactly as batch-1 generate does in the
                 # reference (:222-230) -- its later rows are computed and ignored (rows are independent)
-                step_scores, gen = self._greedy(merged, rows, [g] * len(chunk), max_new_tokens, stops)
+                step_scores, gen = self._greedy(merged, rows, [g] * len(chunk), max_new_tokens, stops, media=[media_of[i] for i in chunk])
                 for k, i in enumerate(chunk):
                     out[i] = (step_scores[k], gen[k], a_ids[k])
         return out
@@ -450,9 +453,15 @@ class Qwen25VLModel(VQAScoreModel):
             x = x.masked_fill(torch.zeros_like(drop).scatter(-1, idx, drop), float("-inf"))
         return x
 
-    def _greedy(self, merged, rows: List[List[int]], grids, max_new_tokens: int, stops: List[int], pick=None):
+    def split_prompt(self, ids: List[int]) -> Tuple[List[int], List[int]]:
+        """build_ids(...) -> (prefix through <|vision_end|>, suffix): the prefix is the same for every question about one medium."""
+        from ...qwen.layout import split_prompt_ids
+        return split_prompt_ids(ids, self.cfg.vision_end_token_id)
+
+    def _greedy(self, merged, rows: List[List[int]], grids, max_new_tokens: int, stops: List[int], pick=None, media=None):
         """Shared generation loop: prompt rows (token id lists, one video run each) -> (per-sample list of processed score rows,
-        per-sample generated ids).  `pick(proc) -> next ids` defaults to argmax (do_sample=False)."""
+        per-sample generated ids).  `pick(proc) -> next ids` defaults to argmax (do_sample=False).  media: the medium of each row;
+        with share_prefix, rows of one medium run their common prompt prefix once (QwenEngine.score_shared)."""
         n = len(rows)
         L = max(len(r) for r in rows)
         ids = torch.zeros(n, L, dtype=torch.long)
@@ -464,7 +473,12 @@ class Qwen25VLModel(VQAScoreModel):
         gen: List[List[int]] = [[] for _ in rows]
         done = [False] * n
         state = None
-        if max_new_tokens == 1:
+        shared = None
+        if getattr(self, "share_prefix", False) and media is not None and hasattr(self.engine, "score_shared"):
+            shared = self.engine.score_shared(merged, ids, mask, grids, media, max_new_tokens)
+        if shared is not None:
+            logits, state = shared
+        elif max_new_tokens == 1:
             logits = self.engine.score_logits(merged, ids, mask, grids)
         else:
             logits, state = self.engine.prefill(merged, ids, mask, grids, max_new_tokens)
@@ -512,7 +526,7 @@ class Qwen25VLModel(VQAScoreModel):
                 merged = torch.cat([merged_of[media_of[i]] for i in chunk])
                 n_tok = g[0] * g[1] * g[2] // self.cfg.vision.merge_unit
                 rows = [self.build_ids(texts[i], kinds[media_of[i]], n_tok) for i in chunk]
-                _, gen = self._greedy(merged, rows, [g] * len(chunk), max_new_tokens, stops, pick)
+                _, gen = self._greedy(merged, rows, [g] * len(chunk), max_new_tokens, stops, pick, media=[media_of[i] for i in chunk])
                 for k, i in enumerate(chunk):
                     out[i] = self.tokenizer.decode(gen[k], skip_special_tokens=True).strip()
         return out

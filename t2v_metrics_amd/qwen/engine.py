@@ -9,7 +9,7 @@ import torch
 
 from ..engine import VqsError, VqsWeightDesc, load_library, _stream_ptr
 from .config import Qwen25VLConfig
-from .layout import text_layout, vision_layout
+from .layout import shared_prefix_plan, text_layout, vision_layout
 
 _i32, _f32, _vp, _sz = ctypes.c_int32, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
@@ -40,6 +40,12 @@ _SIGS = {
     "vqs_qwen_get_option": (_i32, [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
     "vqs_qwen_range_report": (_i32, [_vp, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _i32]),
     "vqs_qwen_score": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "vqs_qwen_prefix_kv_bytes": (_sz, [_vp, _i32, _i32]),
+    "vqs_qwen_prefix_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "vqs_qwen_prefix": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp, _sz, _vp]),
+    "vqs_qwen_suffix_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "vqs_qwen_score_suffix": (_i32, [_vp] + [_vp] * 8 + [_i32, _i32, _i32, _vp, _i32, _sz, _vp, _vp, _sz, _vp]),
+    "vqs_qwen_prefill_suffix": (_i32, [_vp] + [_vp] * 8 + [_i32, _i32, _i32, _vp, _i32, _sz, _vp, _vp, _sz, _vp, _sz, _i32, _vp]),
 }
 
 
@@ -195,6 +201,44 @@ class QwenEngine:
             # pool stalled a step by 70 ms now and then (profiles/r4_call15_*)
             state = {"kv": kv, "len": t["seq_len"].clone(), "Lmax": Lmax, "B": B, "pos": lay["next_pos"].clone().to(dev), "steps": 0,
                      "len_host_max": int(lay["seq_len"].max())}
+            return logits, state
+
+    def score_shared(self, merged: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor, grids: Sequence[Tuple[int, int, int]],
+                     media: Sequence, max_new_tokens: int = 1):
+        """score_logits (max_new_tokens == 1) or prefill, with the prompt prefix of every medium computed once (vqs_qwen_prefix +
+        vqs_qwen_score_suffix / vqs_qwen_prefill_suffix): media[b] names sample b's medium; samples with equal media share their
+        prefix.  Bitwise the unshared results.  -> (logits, decode state or None), or None when no medium has two samples here."""
+        plan = shared_prefix_plan(self.cfg, input_ids.cpu(), attention_mask.cpu(), grids, media)
+        if plan is None:
+            return None
+        with torch.cuda.device(self.device):
+            dev = self.device
+            B, L = input_ids.shape
+            U, Lp, Ls = plan["U"], plan["Lp"], plan["Ls"]
+            self._merged_matches_mode(merged)
+            merged = merged.contiguous()
+            n_vis = merged.shape[0] // B
+            merged_u = merged.view(B, n_vis, -1)[plan["first"]].reshape(U * n_vis, -1).contiguous()
+            t = {k: plan[k].to(dev).contiguous() for k in ("media_idx", "prefix_ids", "prefix_vis_slot", "prefix_cos", "prefix_sin", "suffix_ids",
+                                                         "suffix_vis_slot", "suffix_cos", "suffix_sin", "seq_len", "last_row")}
+            pkv = torch.empty(self.lib.vqs_qwen_prefix_kv_bytes(self._h, U, Lp), dtype=torch.uint8, device=dev)
+            ws = self._workspace(max(self.lib.vqs_qwen_prefix_workspace_bytes(self._h, U, Lp), self.lib.vqs_qwen_suffix_workspace_bytes(self._h, B, Lp, Ls)))
+            self._check(self.lib.vqs_qwen_prefix(self._h, merged_u.data_ptr(), t["prefix_ids"].data_ptr(), t["prefix_vis_slot"].data_ptr(),
+                                                 t["prefix_cos"].data_ptr(), t["prefix_sin"].data_ptr(), U, Lp, pkv.data_ptr(), pkv.numel(),
+                                                 ws.data_ptr(), ws.numel(), _stream_ptr()), "vqs_qwen_prefix")
+            logits = torch.empty(B, self.cfg.text.vocab, dtype=torch.float32, device=dev)
+            args = [self._h, merged.data_ptr(), t["suffix_ids"].data_ptr(), t["suffix_vis_slot"].data_ptr(), t["seq_len"].data_ptr(),
+                    t["last_row"].data_ptr(), t["suffix_cos"].data_ptr(), t["suffix_sin"].data_ptr(), t["media_idx"].data_ptr(), B, Lp, Ls,
+                    pkv.data_ptr(), U, pkv.numel(), logits.data_ptr(), ws.data_ptr(), ws.numel()]
+            if max_new_tokens <= 1:
+                self._check(self.lib.vqs_qwen_score_suffix(*args, _stream_ptr()), "vqs_qwen_score_suffix")
+                return logits, None
+            Lmax = L + int(max_new_tokens) - 1
+            kv = torch.empty(self.lib.vqs_qwen_kv_bytes(self._h, B, Lmax), dtype=torch.uint8, device=dev)
+            self._check(self.lib.vqs_qwen_prefill_suffix(*args, kv.data_ptr(), kv.numel(), Lmax, _stream_ptr()), "vqs_qwen_prefill_suffix")
+            # the same decode state as prefill() (see there)
+            state = {"kv": kv, "len": t["seq_len"].clone(), "Lmax": Lmax, "B": B, "pos": plan["next_pos"].clone().to(dev), "steps": 0,
+                     "len_host_max": int(plan["seq_len"].max())}
             return logits, state
 
     def decode(self, state, token_ids: torch.Tensor) -> torch.Tensor:

@@ -5,7 +5,7 @@ path supports: every video of one vision call has the same (t, h, w) grid (the w
 attention windows at the right / bottom edge of a frame are handled by a padded windowed layout."""
 from __future__ import annotations
 
-from typing import Dict, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -123,3 +123,69 @@ def decode_tables(cfg: Qwen25VLConfig, positions: torch.Tensor) -> Tuple[torch.T
     freqs = positions[..., None].float() * inv_freq                                  # [3, B, hd/2]; on the positions' device
     ang = torch.cat([m[i % 3] for i, m in enumerate(freqs.split(list(cfg.text.mrope_section), dim=-1))], dim=-1)
     return ang.cos().contiguous(), ang.sin().contiguous()
+
+
+def split_prompt_ids(ids: Sequence[int], vision_end_id: int) -> Tuple[List[int], List[int]]:
+    """One prompt's ids -> (prefix, suffix): the prefix ends with (and includes) its <|vision_end|> token, the suffix is the rest."""
+    ids = list(ids)
+    if ids.count(vision_end_id) != 1:
+        raise ValueError("a prompt must hold exactly one <|vision_end|> token")
+    k = ids.index(vision_end_id) + 1
+    return ids[:k], ids[k:]
+
+
+SHARE_ALIGN = 32        # shared rows are a multiple of the attention kernel's 32-row waves (include/vqs_qwen.h, DESIGN.md)
+MIN_SUFFIX = 8          # the q|k|v GEMM's head-major epilogue steps rows by 8 within a sample
+
+
+def shared_prefix_plan(cfg: Qwen25VLConfig, input_ids: torch.Tensor, attention_mask: torch.Tensor, grids: Sequence[Tuple[int, int, int]],
+                       media: Sequence) -> Optional[Dict]:
+    """The shared-prefix form of one text_layout batch (vqs_qwen_prefix / vqs_qwen_score_suffix): samples b with equal media[b] share
+    their prompt prefix.  None when no medium has two samples or the prefix is too short to share.  Every table is a slice of the
+    unshared text_layout's, so both forms read the same numbers.
+      Lp: shared rows = the split after <|vision_end|>, rounded down to a multiple of 32 (and leaving >= 8 suffix rows); Ls = L - Lp
+      media_idx [B] int32 (index into the U distinct media, in order of first appearance), first [U] (each medium's first sample)
+      prefix_ids / prefix_vis_slot [U, Lp] int32 (slots into the U media's merged tokens), prefix_cos / prefix_sin [U*Lp, hd/2]
+      suffix_ids / suffix_vis_slot [B, Ls] int32 (slots into the batch's merged tokens), suffix_cos / suffix_sin [B*Ls, hd/2]
+      seq_len [B] (whole sequences), last_row [B] = b*Ls + seq_len - 1 - Lp, next_pos [3, B]"""
+    B, L = input_ids.shape
+    if len(media) != B:
+        raise ValueError("one medium per sample")
+    order: Dict = {}
+    media_idx = [order.setdefault(m, len(order)) for m in media]
+    U = len(order)
+    if U == B:
+        return None
+    seq_len = attention_mask.long().sum(-1)
+    splits = []
+    for b in range(B):
+        pre, _ = split_prompt_ids(input_ids[b, : int(seq_len[b])].tolist(), cfg.vision_end_token_id)
+        splits.append(len(pre))
+    first = [media_idx.index(u) for u in range(U)]
+    for b in range(B):
+        f = first[media_idx[b]]
+        if splits[b] != splits[f] or not torch.equal(input_ids[b, : splits[b]], input_ids[f, : splits[f]]):
+            raise AssertionError("samples of one medium must share their prompt prefix")
+    Lp = min(splits) // SHARE_ALIGN * SHARE_ALIGN
+    while Lp >= SHARE_ALIGN and L - Lp < MIN_SUFFIX:
+        Lp -= SHARE_ALIGN
+    if Lp < SHARE_ALIGN:
+        return None
+    Ls = L - Lp
+    lay = text_layout(cfg, input_ids, attention_mask, grids)
+    half = lay["cos"].shape[1]
+    cos, sin = lay["cos"].view(B, L, half), lay["sin"].view(B, L, half)
+    vs = lay["vis_slot"]
+    n_vis = (input_ids == cfg.video_token_id).sum(-1)
+    off = torch.cumsum(n_vis, 0) - n_vis                                  # first merged row of each sample
+    fi = torch.tensor(first)
+    off_u = torch.cumsum(n_vis[fi], 0) - n_vis[fi]                        # ... of each medium among the U media
+    pv = vs[fi, :Lp]
+    pv = torch.where(pv >= 0, pv - off[fi, None].to(pv.dtype) + off_u[:, None].to(pv.dtype), pv)
+    return {"Lp": Lp, "Ls": Ls, "U": U, "first": first, "media_idx": torch.tensor(media_idx, dtype=torch.int32),
+            "prefix_ids": input_ids[fi, :Lp].to(torch.int32).contiguous(), "prefix_vis_slot": pv.to(torch.int32).contiguous(),
+            "prefix_cos": cos[fi, :Lp].reshape(-1, half).contiguous(), "prefix_sin": sin[fi, :Lp].reshape(-1, half).contiguous(),
+            "suffix_ids": input_ids[:, Lp:].to(torch.int32).contiguous(), "suffix_vis_slot": vs[:, Lp:].contiguous(),
+            "suffix_cos": cos[:, Lp:].reshape(-1, half).contiguous(), "suffix_sin": sin[:, Lp:].reshape(-1, half).contiguous(),
+            "seq_len": lay["seq_len"], "last_row": (torch.arange(B) * Ls + seq_len - 1 - Lp).to(torch.int32),
+            "next_pos": lay["next_pos"]}
