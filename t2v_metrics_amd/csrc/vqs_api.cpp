@@ -8,6 +8,7 @@
 #include "../../include/vqs.h"
 #include "../../include/vqs_debug.h"
 #include "vqs_kernels.h"
+#include "vqs_blocks.h"
 
 #include <hip/hip_runtime.h>
 
@@ -320,33 +321,7 @@ int get_w(vqs_handle* h, const std::string& name, int64_t numel, const bf16_t** 
         if (_r != VQS_OK) return _r;                             \
     } while (0)
 
-struct GemmCall {
-    const bf16_t* A;
-    const bf16_t* W;
-    void* C;
-    const bf16_t* bias = nullptr;
-    const float* resid = nullptr;
-    int M, N, K;
-    int lda, ldw, ldc;
-    int epi;
-    int S = 0, H = 0, inner = 0;
-    bf16_t* heads[3] = {nullptr, nullptr, nullptr};
-    int batch = 1;
-    long long sA = 0, sW = 0, sC = 0;
-    // fused residual + RMSNorm (see vqs_kernels.h)
-    float* hres = nullptr;
-    int ldh = 0;
-    const bf16_t* lnw = nullptr;
-    float* rowss_out = nullptr;
-    const float* rowss_in = nullptr;
-    int rowss_parts = 0;
-    float rs_invd = 0.0f, rs_eps = 0.0f;
-    int nt_store = 0;          // result rows leave with the non-temporal hint (call sites whose multi-GB output is streamed once)
-    long long split_off = 0;   // EPI_BF16: also store the lo plane of a split-bf16 result at C + split_off (vqs_kernels.h)
-    float acc_scale = 1.0f, out_scale = 1.0f;   // f16 = 3 / 4: the scaled quad families (vqs_kernels.h)
-    int no_stream = 0;         // 1: keep this launch off the stream form (same bits either way)
-    int f16 = 0;               // A, W and the 16-bit result are IEEE fp16 (the fp16 vision tower; quad form only)
-};
+using vqs::GemmCall;   // vqs_blocks.h
 
 int run_gemm(vqs_handle* h, const GemmCall& g, hipStream_t st, const char* what) {
     vqs::GemmParams p;
@@ -440,6 +415,42 @@ int tap_split(vqs_handle* h, const char* stack, int layer, const char* what, con
     return VQS_OK;
 }
 #define TAP2(stack, layer, what, ptr, plane_elems) RUN(tap_split(h, stack, layer, what, ptr, (size_t)(plane_elems), st))
+
+// vqs_encode_images' side of the shared tower block loop (vqs_blocks.h): weights by their HF names, launches through run_gemm
+// (profiling, per-shape cache-policy options), stage taps under "vit.<layer>.<what>".
+struct VitBlocksCtx {
+    vqs_handle* h;
+    hipStream_t st;
+    int weights(int i, vqs::ClipBlockWeights& lw) {
+        const vqs_config& c = h->c;
+        const int hid = c.vis_hidden, mlp = c.vis_mlp;
+        const bool f16 = h->vit_fp16 != 0;
+        const std::string p = "vision.encoder.layers." + std::to_string(i) + ".";
+        GETW(ln1w, p + "layer_norm1.weight", hid);
+        GETW(ln1b, p + "layer_norm1.bias", hid);
+        GETW(ln2w, p + "layer_norm2.weight", hid);
+        GETW(ln2b, p + "layer_norm2.bias", hid);
+        GETW(ow, p + "self_attn.out_proj.weight", (int64_t)hid * hid);
+        GETW(ob, p + "self_attn.out_proj.bias", hid);
+        GETW(f1w, p + "mlp.fc1.weight", (int64_t)mlp * hid);
+        GETW(f1b, p + "mlp.fc1.bias", mlp);
+        GETW(f2w, p + "mlp.fc2.weight", (int64_t)hid * mlp);
+        GETW(f2b, p + "mlp.fc2.bias", hid);
+        lw = vqs::ClipBlockWeights{ln1w, ln1b, ln2w, ln2b, f16 ? h->vit_qkv_w16[i] : h->vit_qkv_w[i], h->vit_qkv_b[i], f16 ? h->vit_out_w16[i] : ow, ob,
+                                   f16 ? h->vit_fc1_w16[i] : f1w, f1b, f16 ? h->vit_fc2_w16[i] : f2w, f2b};
+        return VQS_OK;
+    }
+    int gemm(const GemmCall& g, const char* what) { return run_gemm(h, g, st, what); }
+    hipError_t attention(const vqs::ClipBlockShape& s, const vqs::ClipBlockBufs& w) {
+        vqs::AttnParams a{w.q, w.k, w.v, w.attn, nullptr, nullptr, s.n, s.heads, s.S, 0.125f};
+        a.f16 = s.f16;
+        return vqs::launch_attention(a, st);
+    }
+    int hip(hipError_t e, const char* what) {
+        return e == hipSuccess ? VQS_OK : fail(h, VQS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    int tap(int layer, const char* what, const void* p, size_t bytes) { return ::tap(h, "vit", layer, what, p, bytes, st); }
+};
 
 }  // namespace
 
@@ -810,81 +821,13 @@ int vqs_encode_images(vqs_handle* h, const void* d_pixels, int32_t N, void* d_fe
     TAP("vit", -1, "patch_out", w.patch_out, (size_t)NP * hid);
     TAP("vit", -1, "h0", w.hidden, (size_t)NS * hid);
 
-    // Residual stream protocol: a sub-layer's output GEMM writes bf16 into `delta`; the NEXT norm kernel performs
-    // hidden += delta (written back) and normalises in the same pass.  `pend` is the not-yet-added delta.
-    // Deferred store (norm_defer, every layer but the last): layer_norm2 normalises hidden + delta_attn WITHOUT writing
-    // the stream and the next layer_norm1 stores (hidden + delta_attn) + delta_mlp -- the same fp32 additions in the
-    // same order, 22 instead of 24 bytes per element and layer.
+    // The block loop (residual stream protocol, deferred stores: vqs_blocks.h) is shared with the CLIPScore row's towers.
     const bf16_t* pend = nullptr;
-    const bf16_t* pend_attn = nullptr;
-    for (int i = 0; i < c.vis_layers_run; ++i) {
-        const bool defer = h->norm_defer != 0 && i + 1 < c.vis_layers_run;
-        const std::string p = "vision.encoder.layers." + std::to_string(i) + ".";
-        GETW(ln1w, p + "layer_norm1.weight", hid);
-        GETW(ln1b, p + "layer_norm1.bias", hid);
-        GETW(ln2w, p + "layer_norm2.weight", hid);
-        GETW(ln2b, p + "layer_norm2.bias", hid);
-        GETW(ow, p + "self_attn.out_proj.weight", (int64_t)hid * hid);
-        GETW(ob, p + "self_attn.out_proj.bias", hid);
-        GETW(f1w, p + "mlp.fc1.weight", (int64_t)mlp * hid);
-        GETW(f1b, p + "mlp.fc1.bias", mlp);
-        GETW(f2w, p + "mlp.fc2.weight", (int64_t)hid * mlp);
-        GETW(f2b, p + "mlp.fc2.bias", hid);
-
-        if (pend_attn)
-            HIPCHK(h, vqs::launch_layernorm(w.hidden, pend_attn, ln1w, ln1b, w.xn, 0, NS, hid, c.vis_ln_eps, st, pend, true, f16), "layer_norm1");
-        else
-            HIPCHK(h, vqs::launch_layernorm(w.hidden, pend, ln1w, ln1b, w.xn, 0, NS, hid, c.vis_ln_eps, st, nullptr, true, f16), "layer_norm1");
-        pend = nullptr;
-        pend_attn = nullptr;
-        TAP("vit", i, "xn0", w.xn, (size_t)NS * hid);
-        {
-            GemmCall g{w.xn, f16 ? h->vit_qkv_w16[i] : h->vit_qkv_w[i], nullptr};
-            g.bias = h->vit_qkv_b[i];
-            g.f16 = f16;
-            g.M = NS; g.N = 3 * hid; g.K = hid; g.lda = hid; g.ldw = hid; g.ldc = 0; g.epi = vqs::EPI_HEADS;
-            g.S = Sv; g.H = c.vis_heads; g.inner = hid;
-            g.heads[0] = w.q; g.heads[1] = w.k; g.heads[2] = w.v;
-            RUN(run_gemm(h, g, st, "vit qkv"));
-        }
-        {
-            vqs::AttnParams a{w.q, w.k, w.v, w.attn, nullptr, nullptr, N, c.vis_heads, Sv, 0.125f};
-            a.f16 = f16;
-            TAP("vit", i, "q", w.q, (size_t)NS * hid);
-            TAP("vit", i, "k", w.k, (size_t)NS * hid);
-            TAP("vit", i, "v", w.v, (size_t)NS * hid);
-            HIPCHK(h, vqs::launch_attention(a, st), "vit attention");
-            TAP("vit", i, "attn", w.attn, (size_t)NS * hid);
-        }
-        {
-            GemmCall g{w.attn, f16 ? h->vit_out_w16[i] : ow, w.delta};
-            g.bias = ob;
-            g.f16 = f16;
-            g.M = NS; g.N = hid; g.K = hid; g.lda = hid; g.ldw = hid; g.ldc = hid; g.epi = vqs::EPI_BF16;
-            RUN(run_gemm(h, g, st, "vit out_proj"));
-            TAP("vit", i, "d_attn", w.delta, (size_t)NS * hid);
-        }
-        HIPCHK(h, vqs::launch_layernorm(w.hidden, w.delta, ln2w, ln2b, w.xn, 0, NS, hid, c.vis_ln_eps, st, nullptr, !defer, f16), "layer_norm2");
-        if (defer) pend_attn = w.delta;
-        TAP("vit", i, "xn1", w.xn, (size_t)NS * hid);
-        {
-            GemmCall g{w.xn, f16 ? h->vit_fc1_w16[i] : f1w, w.mid};
-            g.bias = f1b;
-            g.f16 = f16;
-            g.M = NS; g.N = mlp; g.K = hid; g.lda = hid; g.ldw = hid; g.ldc = mlp; g.epi = vqs::EPI_BF16_QGELU;
-            RUN(run_gemm(h, g, st, "vit fc1"));
-            TAP("vit", i, "mid", w.mid, (size_t)NS * mlp);
-        }
-        {
-            bf16_t* dst = defer ? w.delta2 : w.delta;
-            GemmCall g{w.mid, f16 ? h->vit_fc2_w16[i] : f2w, dst};
-            g.bias = f2b;
-            g.f16 = f16;
-            g.M = NS; g.N = hid; g.K = mlp; g.lda = mlp; g.ldw = mlp; g.ldc = hid; g.epi = vqs::EPI_BF16;
-            RUN(run_gemm(h, g, st, "vit fc2"));
-            TAP("vit", i, "d_mlp", dst, (size_t)NS * hid);
-            pend = dst;
-        }
+    {
+        VitBlocksCtx cx{h, st};
+        vqs::ClipBlockShape bs{N, Sv, hid, c.vis_heads, mlp, c.vis_layers_run, c.vis_ln_eps, f16, h->norm_defer != 0, "vit"};
+        vqs::ClipBlockBufs bb{w.hidden, w.delta, w.delta2, w.xn, w.q, w.k, w.v, w.attn, w.mid};
+        RUN(vqs::run_clip_blocks(cx, bs, bb, st, &pend));
     }
     // hidden_states[-2][:, 1:] = hidden + pending fc2 output, CLS dropped, cast to the projector's operand type
     const bool p16 = f16 && h->proj_fp16 != 0;       // operand type of the selected features and the projector
