@@ -7,7 +7,6 @@
 // returns VQS_ERR_HIP and the message says which one.
 #include "../../include/vqs.h"
 #include "../../include/vqs_debug.h"
-#include "vqs_kernels.h"
 #include "vqs_blocks.h"
 
 #include <hip/hip_runtime.h>
@@ -19,38 +18,32 @@
 #include <string>
 #include <unordered_map>
 #include <vector>
-#include <map>
-#include <array>
 
 using vqs::bf16_t;
-
-struct WEntry {
-    const bf16_t* p;
-    int64_t numel;
-};
+using vqs::align_up;
+using vqs::Carver;
+using vqs::fail;
+using vqs::GemmCall;
 
 #if defined(VQS_ATTN_TIMING) && VQS_ATTN_TIMING
 namespace vqs { hipError_t lab_set_attn_timing(unsigned long long* d_buf); }   // attn.hip, timing build only
 #endif
 
-struct vqs_handle {
+struct vqs_handle : vqs::HostBase {
     vqs_config c;
-    std::string err;
-    std::unordered_map<std::string, WEntry> w;
-    bool bound = false;
     int gemm_variant = 0;
     // derived
     int P = 0, Sv = 0, kpatch = 0, kpad = 0, I = 0;
     // packed (device) weights
     const bf16_t* patch_w = nullptr;
-    std::vector<const bf16_t*> vit_qkv_w, vit_qkv_b, enc_qkv, enc_wi, dec_qkv, dec_ckv, dec_wi, dec_ckT;
+    vqs::ClipTower vit;       // q|k|v fused; the fp16 copies serve option vit_fp16
+    std::vector<const bf16_t*> enc_qkv, enc_wi, dec_qkv, dec_ckv, dec_wi, dec_ckT;
     int cross_mode = 1;   // 1 = reassociated cross-attention (default), 0 = per-layer K|V projection of the encoder output
     int stream_gemm = 1;  // 1 = skinny batched launches (M <= 128 rows per entry) take the HBM-streaming GEMM form (gemm_stream.inc; bitwise the 8-wave forms), 0 = never
     int vit_fp16 = 1;     // 1 (default) = the vision tower and the projector run on IEEE fp16 operands (11 significant bits instead of bf16's 8, same MFMA rate and
                           // bytes): fp16 copies of their weights (made at bind time), fp16 activations, fp32 accumulation / residual stream / statistics
                           // as before; the image features leave as bf16 (the C ABI's type).  CLIP was trained in fp16; the T5 stack is NOT fp16-safe
                           // and stays bf16.  0 = the bf16 tower of rounds 1-3 (what the reference's dtype would give)
-    std::vector<const bf16_t*> vit_qkv_w16, vit_out_w16, vit_fc1_w16, vit_fc2_w16;   // the fp16 copies (packed buffer)
     const bf16_t* proj0_w16 = nullptr;
     const bf16_t* proj2_w16 = nullptr;
     int dec_precise = 1;  // 1 = the scoring decoder holds its activations as split-bf16 / fp32 (decoder_pass_precise), 0 = bf16 (rounds 1-3)
@@ -78,23 +71,9 @@ struct vqs_handle {
     const int* lut_causal = nullptr;
     int lut_len = 0;
     std::vector<int> h_lut_bidir, h_lut_causal;
-    // profiling
-    bool prof = false;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
-    std::vector<std::pair<std::string, double>> ev_what;   // per profiled GEMM launch: call-site label, FLOPs
-    std::string prof_report;
     int norm_defer = 1;        // VQS_NORM_DEFER=0: every norm stores the updated fp32 stream (24 instead of 22 B/elem per layer)
     int fused_norm = 0;        // VQS_FUSED_NORM=1: residual update + RMSNorm operand in the o / wo GEMM epilogues (lab; +1 %)
     int splitk = 1;            // VQS_SPLITK=0 disables split-K in the decoder's skinny GEMMs (lab A/B)
-    double prof_flops = 0.0;
-    double prof_bytes = 0.0;   // algorithmic operand + result bytes of the profiled GEMM launches
-    // stage taps (vqs_debug_tap): point name -> (caller buffer, capacity); the pass copies the named intermediate there
-    struct Tap { void* dst; size_t cap; };
-    std::unordered_map<std::string, Tap> taps;
-    // tap window (vqs_debug_tap_window): taps copy outer entries [tap_first, tap_first + tap_count) of tap_outer (pairs of the
-    // running T5 pass / images of the running vision pass; set by the pass); tap_count == 0: whole tensors
-    int tap_first = 0, tap_count = 0, tap_outer = 0;
     // per-shape tile order of the big GEMMs (option "tile_order:<N>x<K>"): a permutation of the tile list, results unchanged
     struct TileOrder { int N, K, gm, ns; };
     std::vector<TileOrder> tile_orders;
@@ -104,28 +83,6 @@ struct vqs_handle {
 };
 
 namespace {
-
-int fail(vqs_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
-}
-
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-// Carves named regions out of a caller buffer; with base == nullptr it only measures.
-struct Carver {
-    char* base;
-    size_t off = 0;
-    std::unordered_map<std::string, size_t>* names;
-    template <typename T>
-    T* take(size_t n, const char* name = nullptr) {
-        off = align_up(off);
-        if (names && name) (*names)[name] = off;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += n * sizeof(T);
-        return p;
-    }
-};
 
 struct EncodeWs {
     bf16_t* im2col;
@@ -156,7 +113,7 @@ EncodeWs carve_encode(const vqs_handle* h, char* base, int N, std::unordered_map
     w.mid = cv.take<bf16_t>(NS * c.vis_mlp);
     w.feat_in = cv.take<bf16_t>(NP * c.vis_hidden);
     w.pmid = cv.take<bf16_t>(NP * c.d_model);
-    w.total = align_up(cv.off);
+    w.total = cv.total();
     return w;
 }
 
@@ -236,7 +193,7 @@ ScoreWs carve_score(const vqs_handle* h, char* base, int B, int L, int T,
     w.logits = cv.take<float>(MT * w.ldl, "logits");
     w.Tc = Tc;
     w.kvcache = Tc > 0 ? cv.take<bf16_t>((size_t)c.dec_layers * B * Tc * 2 * I) : nullptr;
-    w.total = align_up(cv.off);
+    w.total = cv.total();
     return w;
 }
 
@@ -253,14 +210,9 @@ struct PackedLayout {
 
 PackedLayout packed_layout(const vqs_handle* h) {
     const vqs_config& c = h->c;
-    Carver cv{nullptr, 0, nullptr};
+    Carver cv{nullptr};
     PackedLayout pl;
-    auto take = [&](size_t elems) {
-        cv.off = align_up(cv.off);
-        size_t o = cv.off;
-        cv.off += elems * sizeof(bf16_t);
-        return o;
-    };
+    auto take = [&](size_t elems) { return cv.mark(elems * sizeof(bf16_t)); };
     const size_t hid = c.vis_hidden, D = c.d_model, I = h->I, F = c.d_ff;
     pl.patch_w = take(hid * h->kpad);
     for (int i = 0; i < c.vis_layers_run; ++i) {
@@ -293,163 +245,43 @@ PackedLayout packed_layout(const vqs_handle* h) {
     for (int i = 0; i < c.dec_layers; ++i) pl.dec_ckT16.push_back(take(I * D));
     pl.lut_bidir = take(2 * (size_t)(c.rel_max_distance + 1));   // int32 = 2 bf16 slots each
     pl.lut_causal = take(2 * (size_t)(c.rel_max_distance + 1));
-    pl.total = align_up(cv.off);
+    pl.total = cv.total();
     return pl;
 }
 
-#define HIPCHK(h, expr, what)                                                                          \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess)                                                                          \
-            return fail(h, VQS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(_e));             \
-    } while (0)
-
-int get_w(vqs_handle* h, const std::string& name, int64_t numel, const bf16_t** out) {
-    auto it = h->w.find(name);
-    if (it == h->w.end()) return fail(h, VQS_ERR_MISSING_WEIGHT, "missing weight: " + name);
-    if (it->second.numel != numel)
-        return fail(h, VQS_ERR_INVALID, "weight " + name + ": numel " + std::to_string(it->second.numel) +
-                                            " != expected " + std::to_string(numel));
-    *out = it->second.p;
-    return VQS_OK;
-}
-
-#define GETW(var, name, numel)                                   \
-    const bf16_t* var = nullptr;                                 \
-    do {                                                         \
-        int _r = get_w(h, (name), (int64_t)(numel), &var);       \
-        if (_r != VQS_OK) return _r;                             \
-    } while (0)
-
-using vqs::GemmCall;   // vqs_blocks.h
-
-int run_gemm(vqs_handle* h, const GemmCall& g, hipStream_t st, const char* what) {
-    vqs::GemmParams p;
-    p.A = g.A; p.W = g.W; p.C = g.C; p.bias = g.bias; p.resid = g.resid;
-    p.M = g.M; p.N = g.N; p.K = g.K; p.lda = g.lda; p.ldw = g.ldw; p.ldc = g.ldc;
-    p.S = g.S > 0 ? g.S : 1; p.H = g.H; p.inner = g.inner > 0 ? g.inner : 1;
-    p.heads_out[0] = g.heads[0]; p.heads_out[1] = g.heads[1]; p.heads_out[2] = g.heads[2];
-    p.batch = g.batch; p.sA = g.sA; p.sW = g.sW; p.sC = g.sC;
-    p.hres = g.hres; p.ldh = g.ldh; p.lnw = g.lnw; p.rowss_out = g.rowss_out;
-    p.rowss_in = g.rowss_in; p.rowss_parts = g.rowss_parts; p.rs_invd = g.rs_invd; p.rs_eps = g.rs_eps;
+// The handle's say in a launch: option gemm_variant / stream_gemm and the per-shape cache-policy options ("tile_order:", "l2_touch:",
+// "nt_store:"; the latter two for the big launches only -- the decoder shares (N, K)).
+vqs::GemmOpts gemm_opts(const vqs_handle* h, const GemmCall& g) {
+    vqs::GemmOpts o;
+    o.variant = h->gemm_variant;
+    o.stream = h->stream_gemm != 0;
     for (const vqs_handle::TileOrder& t : h->tile_orders)
-        if (t.N == g.N && t.K == g.K) { p.tile_gm = t.gm; p.tile_ns = t.ns; }
-    p.nt_store = g.nt_store;
-    p.split_off = g.split_off;
-    p.f16 = g.f16; p.acc_scale = g.acc_scale; p.out_scale = g.out_scale;
-    p.no_stream = (h->stream_gemm && !g.no_stream) ? 0 : 1;
+        if (t.N == g.N && t.K == g.K) { o.tile_gm = t.gm; o.tile_ns = t.ns; }
     for (const vqs_handle::NtStore& t : h->l2_touches)
-        if (t.N == g.N && t.K == g.K && g.M >= 4096) p.l2_touch = t.on;
+        if (t.N == g.N && t.K == g.K && g.M >= 4096) o.l2_touch = t.on;
     for (const vqs_handle::NtStore& t : h->nt_stores)
-        if (t.N == g.N && t.K == g.K && g.M >= 4096) p.nt_store = t.on == 1;      // the big launches only (the decoder shares (N, K))
-    if (h->prof) {
-        while (h->ev.size() < h->ev_used + 2) {
-            hipEvent_t e;
-            HIPCHK(h, hipEventCreate(&e), "hipEventCreate");
-            h->ev.push_back(e);
-        }
-        HIPCHK(h, hipEventRecord(h->ev[h->ev_used], st), "hipEventRecord");
-    }
-    HIPCHK(h, vqs::launch_gemm(p, g.epi, g.batch > 1 ? 3 : h->gemm_variant, st), std::string("gemm ") + what);
-    if (h->prof) {
-        HIPCHK(h, hipEventRecord(h->ev[h->ev_used + 1], st), "hipEventRecord");
-        h->ev_used += 2;
-        h->ev_what.emplace_back(what, 2.0 * (double)g.M * (double)g.N * (double)g.K * (double)g.batch);
-        h->prof_flops += 2.0 * (double)g.M * (double)g.N * (double)g.K * (double)g.batch;
-        {   // every operand read once, every result written once
-            const double out_b = (g.epi == vqs::EPI_F32 || g.epi == vqs::EPI_F32_RESID) ? 4.0 : (g.epi == vqs::EPI_RESID_RMS ? 10.0 : 2.0);
-            const double out_n = (g.epi == vqs::EPI_GATED) ? 0.5 * (double)g.N : (double)g.N;
-            h->prof_bytes += (double)g.batch * (2.0 * ((double)g.M + (double)g.N) * (double)g.K + out_b * (double)g.M * out_n);
-        }
-    }
-    return VQS_OK;
+        if (t.N == g.N && t.K == g.K && g.M >= 4096) o.nt_store = t.on == 1;
+    return o;
 }
+int run_gemm(vqs_handle* h, const GemmCall& g, hipStream_t st, const char* what) { return vqs::run_gemm(h, g, gemm_opts(h, g), st, what); }
 
-#define RUN(expr)                    \
-    do {                             \
-        int _r = (expr);             \
-        if (_r != VQS_OK) return _r; \
-    } while (0)
-
-// Copy an intermediate to a caller buffer registered with vqs_debug_tap (in-stream, device to device).  The workspace
-// buffers are reused layer after layer, so the parity tests that check EVERY launch of a pass against the oracle on the
-// engine's own inputs (tests/test_gpu_stage_locked.py) read them through this.  One empty() test when nothing is registered.
-int tap(vqs_handle* h, const char* stack, int layer, const char* what, const void* src, size_t bytes, hipStream_t st) {
-    if (h->taps.empty()) return VQS_OK;
-    const std::string name = layer >= 0 ? std::string(stack) + "." + std::to_string(layer) + "." + what : std::string(stack) + "." + what;
-    auto it = h->taps.find(name);
-    if (it == h->taps.end()) return VQS_OK;
-    if (h->tap_count > 0) {        // every intermediate is outer-entry-major: the window is one contiguous byte range of it
-        if (h->tap_outer <= 0 || h->tap_first + h->tap_count > h->tap_outer || bytes % (size_t)h->tap_outer != 0)
-            return fail(h, VQS_ERR_INVALID, "tap " + name + ": window [" + std::to_string(h->tap_first) + ", +" + std::to_string(h->tap_count) +
-                                            ") does not fit " + std::to_string(h->tap_outer) + " outer entries");
-        const size_t per = bytes / (size_t)h->tap_outer;
-        src = static_cast<const char*>(src) + per * (size_t)h->tap_first;
-        bytes = per * (size_t)h->tap_count;
-    }
-    if (it->second.cap < bytes) return fail(h, VQS_ERR_WORKSPACE, "tap " + name + ": buffer too small (" + std::to_string(bytes) + " bytes needed)");
-    HIPCHK(h, hipMemcpyAsync(it->second.dst, src, bytes, hipMemcpyDeviceToDevice, st), "tap copy");
-    return VQS_OK;
-}
-#define TAP(stack, layer, what, ptr, elems) RUN(tap(h, stack, layer, what, ptr, (size_t)(elems) * sizeof(*(ptr)), st))
-
-// A split-bf16 tensor (planes [2][rows][width], `plane` elements apart) goes to its tap buffer as two planes of the tapped rows:
-// [2][window rows][width] bf16; the reader adds them (tests/gpu_util.py).
-int tap_split(vqs_handle* h, const char* stack, int layer, const char* what, const bf16_t* src, size_t plane, hipStream_t st) {
-    if (h->taps.empty()) return VQS_OK;
-    const std::string name = layer >= 0 ? std::string(stack) + "." + std::to_string(layer) + "." + what : std::string(stack) + "." + what;
-    auto it = h->taps.find(name);
-    if (it == h->taps.end()) return VQS_OK;
-    size_t bytes = plane * sizeof(bf16_t), first = 0;
-    if (h->tap_count > 0) {
-        if (h->tap_outer <= 0 || h->tap_first + h->tap_count > h->tap_outer || bytes % (size_t)h->tap_outer != 0)
-            return fail(h, VQS_ERR_INVALID, "tap " + name + ": window does not fit");
-        const size_t per = bytes / (size_t)h->tap_outer;
-        first = per * (size_t)h->tap_first;
-        bytes = per * (size_t)h->tap_count;
-    }
-    if (it->second.cap < 2 * bytes) return fail(h, VQS_ERR_WORKSPACE, "tap " + name + ": buffer too small (" + std::to_string(2 * bytes) + " bytes needed)");
-    for (int pl = 0; pl < 2; ++pl)
-        HIPCHK(h, hipMemcpyAsync(static_cast<char*>(it->second.dst) + pl * bytes, reinterpret_cast<const char*>(src + pl * plane) + first, bytes,
-                                 hipMemcpyDeviceToDevice, st), "tap copy");
-    return VQS_OK;
-}
-#define TAP2(stack, layer, what, ptr, plane_elems) RUN(tap_split(h, stack, layer, what, ptr, (size_t)(plane_elems), st))
+#define TAP2(stack, layer, what, ptr, plane_elems) VQS_RUN(vqs::tap_split(h, stack, layer, what, ptr, (size_t)(plane_elems), st))
 
 // vqs_encode_images' side of the shared tower block loop (vqs_blocks.h): weights by their HF names, launches through run_gemm
-// (profiling, per-shape cache-policy options), stage taps under "vit.<layer>.<what>".
+// (per-shape cache-policy options), stage taps under "vit.<layer>.<what>".
 struct VitBlocksCtx {
     vqs_handle* h;
     hipStream_t st;
     int weights(int i, vqs::ClipBlockWeights& lw) {
-        const vqs_config& c = h->c;
-        const int hid = c.vis_hidden, mlp = c.vis_mlp;
-        const bool f16 = h->vit_fp16 != 0;
-        const std::string p = "vision.encoder.layers." + std::to_string(i) + ".";
-        GETW(ln1w, p + "layer_norm1.weight", hid);
-        GETW(ln1b, p + "layer_norm1.bias", hid);
-        GETW(ln2w, p + "layer_norm2.weight", hid);
-        GETW(ln2b, p + "layer_norm2.bias", hid);
-        GETW(ow, p + "self_attn.out_proj.weight", (int64_t)hid * hid);
-        GETW(ob, p + "self_attn.out_proj.bias", hid);
-        GETW(f1w, p + "mlp.fc1.weight", (int64_t)mlp * hid);
-        GETW(f1b, p + "mlp.fc1.bias", mlp);
-        GETW(f2w, p + "mlp.fc2.weight", (int64_t)hid * mlp);
-        GETW(f2b, p + "mlp.fc2.bias", hid);
-        lw = vqs::ClipBlockWeights{ln1w, ln1b, ln2w, ln2b, f16 ? h->vit_qkv_w16[i] : h->vit_qkv_w[i], h->vit_qkv_b[i], f16 ? h->vit_out_w16[i] : ow, ob,
-                                   f16 ? h->vit_fc1_w16[i] : f1w, f1b, f16 ? h->vit_fc2_w16[i] : f2w, f2b};
-        return VQS_OK;
+        return vqs::clip_block_weights(h, "vision.", i, h->c.vis_hidden, h->c.vis_mlp, h->vit_fp16 != 0, h->vit, lw);
     }
-    int gemm(const GemmCall& g, const char* what) { return run_gemm(h, g, st, what); }
+    vqs::GemmOpts gemm_opts(const GemmCall& g) const { return ::gemm_opts(h, g); }
     hipError_t attention(const vqs::ClipBlockShape& s, const vqs::ClipBlockBufs& w) {
         vqs::AttnParams a{w.q, w.k, w.v, w.attn, nullptr, nullptr, s.n, s.heads, s.S, 0.125f};
         a.f16 = s.f16;
         return vqs::launch_attention(a, st);
     }
-    int hip(hipError_t e, const char* what) {
-        return e == hipSuccess ? VQS_OK : fail(h, VQS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    }
-    int tap(int layer, const char* what, const void* p, size_t bytes) { return ::tap(h, "vit", layer, what, p, bytes, st); }
+    int tap(int layer, const char* what, const void* p, size_t bytes) { return vqs::tap(h, "vit", layer, what, p, bytes, st); }
 };
 
 }  // namespace
@@ -458,16 +290,14 @@ extern "C" {
 
 int vqs_debug_tap(vqs_handle* h, const char* name, void* d_dst, size_t bytes) {
     if (!h) return VQS_ERR_INVALID;
-    if (!name) { h->taps.clear(); return VQS_OK; }
-    if (!d_dst || bytes == 0) { h->taps.erase(name); return VQS_OK; }
-    h->taps[name] = vqs_handle::Tap{d_dst, bytes};
+    h->taps.set(name, d_dst, bytes);
     return VQS_OK;
 }
 
 int vqs_debug_tap_window(vqs_handle* h, int32_t first, int32_t count) {
     if (!h || first < 0 || count < 0) return VQS_ERR_INVALID;
-    h->tap_first = count > 0 ? first : 0;
-    h->tap_count = count;
+    h->taps.first = count > 0 ? first : 0;
+    h->taps.count = count;
     return VQS_OK;
 }
 
@@ -652,11 +482,7 @@ int vqs_get_option(const vqs_handle* h, const char* name, int32_t* value) {
     return VQS_OK;
 }
 
-void vqs_destroy(vqs_handle* h) {
-    if (!h) return;
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    delete h;
-}
+void vqs_destroy(vqs_handle* h) { delete h; }      // ~GemmProfile destroys the profile's events
 
 const char* vqs_last_error(const vqs_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
@@ -670,109 +496,105 @@ int vqs_bind_weights(vqs_handle* h, const vqs_weight_desc* weights, int32_t n, v
     const PackedLayout pl = packed_layout(h);
     if (packed_bytes < pl.total) return fail(h, VQS_ERR_WORKSPACE, "bind_weights: packed buffer too small");
     h->bound = false;
-    h->w.clear();
-    for (int i = 0; i < n; ++i) {
-        if (!weights[i].name || !weights[i].d_data) return fail(h, VQS_ERR_INVALID, "bind_weights: null entry");
-        h->w[weights[i].name] = WEntry{(const bf16_t*)weights[i].d_data, weights[i].numel};
-    }
+    VQS_RUN(vqs::set_weights(h, weights, n));
     char* pk = (char*)d_packed;
     auto at = [&](size_t off) { return reinterpret_cast<bf16_t*>(pk + off); };
     const int hid = c.vis_hidden, D = c.d_model, I = h->I, F = c.d_ff;
 
     // conv kernel [hid, 3*p*p] -> [hid, kpad] zero padded (K must be a multiple of 64)
     {
-        GETW(pw, "vision.embeddings.patch_embedding.weight", (int64_t)hid * h->kpatch);
-        HIPCHK(h, vqs::launch_copy_rows(pw, at(pl.patch_w), hid, h->kpatch, h->kpatch, h->kpad, 0, st), "pack patch");
+        VQS_W(pw, "vision.embeddings.patch_embedding.weight", (int64_t)hid * h->kpatch);
+        VQS_HIP(h, vqs::launch_copy_rows(pw, at(pl.patch_w), hid, h->kpatch, h->kpatch, h->kpad, 0, st), "pack patch");
         h->patch_w = at(pl.patch_w);
     }
-    h->vit_qkv_w.clear(); h->vit_qkv_b.clear();
+    h->vit.qkv_w.clear(); h->vit.qkv_b.clear();
     for (int i = 0; i < c.vis_layers_run; ++i) {
         const std::string p = "vision.encoder.layers." + std::to_string(i) + ".self_attn.";
         const char* nm[3] = {"q_proj", "k_proj", "v_proj"};
         for (int j = 0; j < 3; ++j) {
-            GETW(ww, p + nm[j] + ".weight", (int64_t)hid * hid);
-            GETW(bb, p + nm[j] + ".bias", hid);
-            HIPCHK(h, vqs::launch_copy_rows(ww, at(pl.vit_qkv_w[i]), hid, hid, hid, hid, j * hid, st), "pack vit qkv");
-            HIPCHK(h, vqs::launch_copy_rows(bb, at(pl.vit_qkv_b[i]), 1, hid, hid, hid, j, st), "pack vit qkv bias");
+            VQS_W(ww, p + nm[j] + ".weight", (int64_t)hid * hid);
+            VQS_W(bb, p + nm[j] + ".bias", hid);
+            VQS_HIP(h, vqs::launch_copy_rows(ww, at(pl.vit_qkv_w[i]), hid, hid, hid, hid, j * hid, st), "pack vit qkv");
+            VQS_HIP(h, vqs::launch_copy_rows(bb, at(pl.vit_qkv_b[i]), 1, hid, hid, hid, j, st), "pack vit qkv bias");
         }
-        h->vit_qkv_w.push_back(at(pl.vit_qkv_w[i]));
-        h->vit_qkv_b.push_back(at(pl.vit_qkv_b[i]));
+        h->vit.qkv_w.push_back(at(pl.vit_qkv_w[i]));
+        h->vit.qkv_b.push_back(at(pl.vit_qkv_b[i]));
     }
     // fp16 copies of the tower's and the projector's linear weights (option vit_fp16): bf16 -> fp16 is exact for 2^-14 <= |w| < 65 520
-    h->vit_qkv_w16.clear(); h->vit_out_w16.clear(); h->vit_fc1_w16.clear(); h->vit_fc2_w16.clear();
+    h->vit.qkv_w16.clear(); h->vit.out_w16.clear(); h->vit.fc1_w16.clear(); h->vit.fc2_w16.clear();
     for (int i = 0; i < c.vis_layers_run; ++i) {
         const std::string p = "vision.encoder.layers." + std::to_string(i) + ".";
         const size_t mlp = (size_t)c.vis_mlp;
-        GETW(ow, p + "self_attn.out_proj.weight", (int64_t)hid * hid);
-        GETW(f1w, p + "mlp.fc1.weight", (int64_t)mlp * hid);
-        GETW(f2w, p + "mlp.fc2.weight", (int64_t)hid * mlp);
-        HIPCHK(h, vqs::launch_cast16(at(pl.vit_qkv_w[i]), at(pl.vit_qkv_w16[i]), (size_t)3 * hid * hid, true, st), "fp16 vit qkv");
-        HIPCHK(h, vqs::launch_cast16(ow, at(pl.vit_out_w16[i]), (size_t)hid * hid, true, st), "fp16 vit out_proj");
-        HIPCHK(h, vqs::launch_cast16(f1w, at(pl.vit_fc1_w16[i]), mlp * hid, true, st), "fp16 vit fc1");
-        HIPCHK(h, vqs::launch_cast16(f2w, at(pl.vit_fc2_w16[i]), mlp * hid, true, st), "fp16 vit fc2");
-        h->vit_qkv_w16.push_back(at(pl.vit_qkv_w16[i]));
-        h->vit_out_w16.push_back(at(pl.vit_out_w16[i]));
-        h->vit_fc1_w16.push_back(at(pl.vit_fc1_w16[i]));
-        h->vit_fc2_w16.push_back(at(pl.vit_fc2_w16[i]));
+        VQS_W(ow, p + "self_attn.out_proj.weight", (int64_t)hid * hid);
+        VQS_W(f1w, p + "mlp.fc1.weight", (int64_t)mlp * hid);
+        VQS_W(f2w, p + "mlp.fc2.weight", (int64_t)hid * mlp);
+        VQS_HIP(h, vqs::launch_cast16(at(pl.vit_qkv_w[i]), at(pl.vit_qkv_w16[i]), (size_t)3 * hid * hid, true, st), "fp16 vit qkv");
+        VQS_HIP(h, vqs::launch_cast16(ow, at(pl.vit_out_w16[i]), (size_t)hid * hid, true, st), "fp16 vit out_proj");
+        VQS_HIP(h, vqs::launch_cast16(f1w, at(pl.vit_fc1_w16[i]), mlp * hid, true, st), "fp16 vit fc1");
+        VQS_HIP(h, vqs::launch_cast16(f2w, at(pl.vit_fc2_w16[i]), mlp * hid, true, st), "fp16 vit fc2");
+        h->vit.qkv_w16.push_back(at(pl.vit_qkv_w16[i]));
+        h->vit.out_w16.push_back(at(pl.vit_out_w16[i]));
+        h->vit.fc1_w16.push_back(at(pl.vit_fc1_w16[i]));
+        h->vit.fc2_w16.push_back(at(pl.vit_fc2_w16[i]));
     }
     {
-        GETW(p0w, "mm_projector.0.weight", (int64_t)D * hid);
-        GETW(p2w, "mm_projector.2.weight", (int64_t)D * D);
-        HIPCHK(h, vqs::launch_cast16(p0w, at(pl.proj0_w16), (size_t)D * hid, true, st), "fp16 mm_projector.0");
-        HIPCHK(h, vqs::launch_cast16(p2w, at(pl.proj2_w16), (size_t)D * D, true, st), "fp16 mm_projector.2");
+        VQS_W(p0w, "mm_projector.0.weight", (int64_t)D * hid);
+        VQS_W(p2w, "mm_projector.2.weight", (int64_t)D * D);
+        VQS_HIP(h, vqs::launch_cast16(p0w, at(pl.proj0_w16), (size_t)D * hid, true, st), "fp16 mm_projector.0");
+        VQS_HIP(h, vqs::launch_cast16(p2w, at(pl.proj2_w16), (size_t)D * D, true, st), "fp16 mm_projector.2");
         h->proj0_w16 = at(pl.proj0_w16);
         h->proj2_w16 = at(pl.proj2_w16);
     }
     auto pack_qkv = [&](const std::string& prefix, bf16_t* dst, int first, int count) -> int {
         const char* nm[3] = {"q", "k", "v"};
         for (int j = 0; j < count; ++j) {
-            GETW(ww, prefix + nm[first + j] + ".weight", (int64_t)I * D);
-            HIPCHK(h, vqs::launch_copy_rows(ww, dst, I, D, D, D, j * I, st), "pack t5 qkv");
+            VQS_W(ww, prefix + nm[first + j] + ".weight", (int64_t)I * D);
+            VQS_HIP(h, vqs::launch_copy_rows(ww, dst, I, D, D, D, j * I, st), "pack t5 qkv");
         }
         return VQS_OK;
     };
     auto pack_wi = [&](const std::string& prefix, bf16_t* dst) -> int {
-        GETW(w0, prefix + "wi_0.weight", (int64_t)F * D);
-        GETW(w1, prefix + "wi_1.weight", (int64_t)F * D);
-        HIPCHK(h, vqs::launch_interleave_gate(w0, w1, dst, F, D, st), "pack wi");
+        VQS_W(w0, prefix + "wi_0.weight", (int64_t)F * D);
+        VQS_W(w1, prefix + "wi_1.weight", (int64_t)F * D);
+        VQS_HIP(h, vqs::launch_interleave_gate(w0, w1, dst, F, D, st), "pack wi");
         return VQS_OK;
     };
     h->enc_qkv16.clear(); h->enc_o16.clear(); h->enc_wi16.clear(); h->dec_ckT16.clear();
     h->enc_qkv.clear(); h->enc_wi.clear(); h->dec_qkv.clear(); h->dec_ckv.clear(); h->dec_wi.clear(); h->dec_ckT.clear();
     for (int i = 0; i < c.enc_layers; ++i) {
         const std::string p = "encoder.block." + std::to_string(i) + ".";
-        RUN(pack_qkv(p + "layer.0.SelfAttention.", at(pl.enc_qkv[i]), 0, 3));
-        RUN(pack_wi(p + "layer.1.DenseReluDense.", at(pl.enc_wi[i])));
+        VQS_RUN(pack_qkv(p + "layer.0.SelfAttention.", at(pl.enc_qkv[i]), 0, 3));
+        VQS_RUN(pack_wi(p + "layer.1.DenseReluDense.", at(pl.enc_wi[i])));
         h->enc_qkv.push_back(at(pl.enc_qkv[i]));
         h->enc_wi.push_back(at(pl.enc_wi[i]));
         // fp16 copies for option enc_fp16 (of the PACKED q|k|v and interleaved wi_0|wi_1, and of o): exact for 2^-14 <= |w| < 65 520
-        GETW(ow, p + "layer.0.SelfAttention.o.weight", (int64_t)D * I);
-        HIPCHK(h, vqs::launch_cast16(at(pl.enc_qkv[i]), at(pl.enc_qkv16[i]), (size_t)3 * I * D, true, st), "fp16 enc qkv");
-        HIPCHK(h, vqs::launch_cast16(ow, at(pl.enc_o16[i]), (size_t)D * I, true, st), "fp16 enc o");
-        HIPCHK(h, vqs::launch_cast16(at(pl.enc_wi[i]), at(pl.enc_wi16[i]), (size_t)2 * F * D, true, st), "fp16 enc wi");
+        VQS_W(ow, p + "layer.0.SelfAttention.o.weight", (int64_t)D * I);
+        VQS_HIP(h, vqs::launch_cast16(at(pl.enc_qkv[i]), at(pl.enc_qkv16[i]), (size_t)3 * I * D, true, st), "fp16 enc qkv");
+        VQS_HIP(h, vqs::launch_cast16(ow, at(pl.enc_o16[i]), (size_t)D * I, true, st), "fp16 enc o");
+        VQS_HIP(h, vqs::launch_cast16(at(pl.enc_wi[i]), at(pl.enc_wi16[i]), (size_t)2 * F * D, true, st), "fp16 enc wi");
         h->enc_qkv16.push_back(at(pl.enc_qkv16[i]));
         h->enc_o16.push_back(at(pl.enc_o16[i]));
         h->enc_wi16.push_back(at(pl.enc_wi16[i]));
     }
     for (int i = 0; i < c.dec_layers; ++i) {
         const std::string p = "decoder.block." + std::to_string(i) + ".";
-        RUN(pack_qkv(p + "layer.0.SelfAttention.", at(pl.dec_qkv[i]), 0, 3));
-        RUN(pack_qkv(p + "layer.1.EncDecAttention.", at(pl.dec_ckv[i]), 1, 2));
-        RUN(pack_wi(p + "layer.2.DenseReluDense.", at(pl.dec_wi[i])));
+        VQS_RUN(pack_qkv(p + "layer.0.SelfAttention.", at(pl.dec_qkv[i]), 0, 3));
+        VQS_RUN(pack_qkv(p + "layer.1.EncDecAttention.", at(pl.dec_ckv[i]), 1, 2));
+        VQS_RUN(pack_wi(p + "layer.2.DenseReluDense.", at(pl.dec_wi[i])));
         h->dec_qkv.push_back(at(pl.dec_qkv[i]));
         h->dec_ckv.push_back(at(pl.dec_ckv[i]));
         {   // Wk^T [D, I] for the reassociated cross-attention: q'_h = q_h . Wk_h needs Wk_h^T K-contiguous
-            GETW(wk, p + "layer.1.EncDecAttention.k.weight", (int64_t)I * D);
-            HIPCHK(h, vqs::launch_transpose(wk, at(pl.dec_ckT[i]), I, D, st), "pack cross k^T");
+            VQS_W(wk, p + "layer.1.EncDecAttention.k.weight", (int64_t)I * D);
+            VQS_HIP(h, vqs::launch_transpose(wk, at(pl.dec_ckT[i]), I, D, st), "pack cross k^T");
             h->dec_ckT.push_back(at(pl.dec_ckT[i]));
-            HIPCHK(h, vqs::launch_cast16(at(pl.dec_ckT[i]), at(pl.dec_ckT16[i]), (size_t)I * D, true, st), "fp16 cross k^T");
+            VQS_HIP(h, vqs::launch_cast16(at(pl.dec_ckT[i]), at(pl.dec_ckT16[i]), (size_t)I * D, true, st), "fp16 cross k^T");
             h->dec_ckT16.push_back(at(pl.dec_ckT16[i]));
         }
         h->dec_wi.push_back(at(pl.dec_wi[i]));
     }
-    HIPCHK(h, hipMemcpyAsync(pk + pl.lut_bidir, h->h_lut_bidir.data(), h->lut_len * sizeof(int), hipMemcpyHostToDevice, st),
+    VQS_HIP(h, hipMemcpyAsync(pk + pl.lut_bidir, h->h_lut_bidir.data(), h->lut_len * sizeof(int), hipMemcpyHostToDevice, st),
            "upload bucket lut");
-    HIPCHK(h, hipMemcpyAsync(pk + pl.lut_causal, h->h_lut_causal.data(), h->lut_len * sizeof(int), hipMemcpyHostToDevice, st),
+    VQS_HIP(h, hipMemcpyAsync(pk + pl.lut_causal, h->h_lut_causal.data(), h->lut_len * sizeof(int), hipMemcpyHostToDevice, st),
            "upload bucket lut");
     h->lut_bidir = reinterpret_cast<const int*>(pk + pl.lut_bidir);
     h->lut_causal = reinterpret_cast<const int*>(pk + pl.lut_causal);
@@ -796,7 +618,7 @@ int vqs_encode_images(vqs_handle* h, const void* d_pixels, int32_t N, void* d_fe
     hipStream_t st = (hipStream_t)stream;
     const int hid = c.vis_hidden, P = h->P, Sv = h->Sv, mlp = c.vis_mlp, D = c.d_model;
     const int NP = N * P, NS = N * Sv;
-    h->tap_outer = N;
+    h->taps.outer = N;
     // option vit_fp16: every 16-bit tensor of the tower and the projector (norm outputs, q / k / v, attention output, deltas, FFN
     // product, selected features, projector hidden) is IEEE fp16 and every linear reads the fp16 copy of its weight; the fp32 residual
     // stream, the norm statistics, the softmax and all accumulation are what they were.  The patch embedding (fp32 result) keeps its
@@ -805,21 +627,21 @@ int vqs_encode_images(vqs_handle* h, const void* d_pixels, int32_t N, void* d_fe
     if (f16 && h->gemm_variant != 3)
         return fail(h, VQS_ERR_STATE, "encode_images: the fp16 vision tower (option vit_fp16, default 1) needs gemm_variant 3 -- its linears exist in the quad form only; set vit_fp16=0 to A/B other GEMM forms");
 
-    GETW(cls, "vision.embeddings.class_embedding", hid);
-    GETW(pos, "vision.embeddings.position_embedding.weight", (int64_t)Sv * hid);
-    GETW(pre_w, "vision.pre_layrnorm.weight", hid);
-    GETW(pre_b, "vision.pre_layrnorm.bias", hid);
+    VQS_W(cls, "vision.embeddings.class_embedding", hid);
+    VQS_W(pos, "vision.embeddings.position_embedding.weight", (int64_t)Sv * hid);
+    VQS_W(pre_w, "vision.pre_layrnorm.weight", hid);
+    VQS_W(pre_b, "vision.pre_layrnorm.bias", hid);
 
-    HIPCHK(h, vqs::launch_im2col((const bf16_t*)d_pixels, w.im2col, N, c.vis_image, c.vis_patch, h->kpad, st), "im2col");
+    VQS_HIP(h, vqs::launch_im2col((const bf16_t*)d_pixels, w.im2col, N, c.vis_image, c.vis_patch, h->kpad, st), "im2col");
     {
         GemmCall g{w.im2col, h->patch_w, w.patch_out};
         g.M = NP; g.N = hid; g.K = h->kpad; g.lda = h->kpad; g.ldw = h->kpad; g.ldc = hid; g.epi = vqs::EPI_F32;
-        RUN(run_gemm(h, g, st, "patch_embed"));
+        VQS_RUN(run_gemm(h, g, st, "patch_embed"));
     }
-    HIPCHK(h, vqs::launch_vit_assemble(w.patch_out, cls, pos, w.pre, N, P, hid, st), "vit_assemble");
-    HIPCHK(h, vqs::launch_layernorm(w.pre, nullptr, pre_w, pre_b, w.hidden, 1, NS, hid, c.vis_ln_eps, st), "pre_layrnorm");
-    TAP("vit", -1, "patch_out", w.patch_out, (size_t)NP * hid);
-    TAP("vit", -1, "h0", w.hidden, (size_t)NS * hid);
+    VQS_HIP(h, vqs::launch_vit_assemble(w.patch_out, cls, pos, w.pre, N, P, hid, st), "vit_assemble");
+    VQS_HIP(h, vqs::launch_layernorm(w.pre, nullptr, pre_w, pre_b, w.hidden, 1, NS, hid, c.vis_ln_eps, st), "pre_layrnorm");
+    VQS_TAP("vit", -1, "patch_out", w.patch_out, (size_t)NP * hid);
+    VQS_TAP("vit", -1, "h0", w.hidden, (size_t)NS * hid);
 
     // The block loop (residual stream protocol, deferred stores: vqs_blocks.h) is shared with the CLIPScore row's towers.
     const bf16_t* pend = nullptr;
@@ -827,26 +649,26 @@ int vqs_encode_images(vqs_handle* h, const void* d_pixels, int32_t N, void* d_fe
         VitBlocksCtx cx{h, st};
         vqs::ClipBlockShape bs{N, Sv, hid, c.vis_heads, mlp, c.vis_layers_run, c.vis_ln_eps, f16, h->norm_defer != 0, "vit"};
         vqs::ClipBlockBufs bb{w.hidden, w.delta, w.delta2, w.xn, w.q, w.k, w.v, w.attn, w.mid};
-        RUN(vqs::run_clip_blocks(cx, bs, bb, st, &pend));
+        VQS_RUN(vqs::run_clip_blocks(cx, bs, bb, st, &pend));
     }
     // hidden_states[-2][:, 1:] = hidden + pending fc2 output, CLS dropped, cast to the projector's operand type
     const bool p16 = f16 && h->proj_fp16 != 0;       // operand type of the selected features and the projector
     const bool psc = p16 && (h->proj_fs_shift != 0 || h->proj_mid_shift != 0);      // scaled forms only where the proof asked for a scale
     const float s_fs = psc ? std::ldexp(1.0f, -h->proj_fs_shift) : 1.0f, s_mid = psc ? std::ldexp(1.0f, -h->proj_mid_shift) : 1.0f;
-    HIPCHK(h, vqs::launch_drop_cls_cast(w.hidden, pend, w.feat_in, N, P, hid, st, f16, p16 ? 1 : 0, s_fs), "feature select");
-    TAP("vit", -1, "feat_in", w.feat_in, (size_t)NP * hid);
-    GETW(p0w, "mm_projector.0.weight", (int64_t)D * hid);
-    GETW(p0b, "mm_projector.0.bias", D);
-    GETW(p2w, "mm_projector.2.weight", (int64_t)D * D);
-    GETW(p2b, "mm_projector.2.bias", D);
+    VQS_HIP(h, vqs::launch_drop_cls_cast(w.hidden, pend, w.feat_in, N, P, hid, st, f16, p16 ? 1 : 0, s_fs), "feature select");
+    VQS_TAP("vit", -1, "feat_in", w.feat_in, (size_t)NP * hid);
+    VQS_W(p0w, "mm_projector.0.weight", (int64_t)D * hid);
+    VQS_W(p0b, "mm_projector.0.bias", D);
+    VQS_W(p2w, "mm_projector.2.weight", (int64_t)D * D);
+    VQS_W(p2b, "mm_projector.2.bias", D);
     {
         GemmCall g{w.feat_in, p16 ? h->proj0_w16 : p0w, w.pmid};
         g.bias = p0b;
         g.f16 = psc ? 3 : (p16 ? 1 : 0);
         g.acc_scale = 1.0f / s_fs; g.out_scale = s_mid;
         g.M = NP; g.N = D; g.K = hid; g.lda = hid; g.ldw = hid; g.ldc = D; g.epi = vqs::EPI_BF16_GELU;
-        RUN(run_gemm(h, g, st, "mm_projector.0"));
-        TAP("vit", -1, "pmid", w.pmid, (size_t)NP * D);
+        VQS_RUN(run_gemm(h, g, st, "mm_projector.0"));
+        VQS_TAP("vit", -1, "pmid", w.pmid, (size_t)NP * D);
     }
     {
         // the image features are a bf16 tensor of the C ABI (vqs_score reads them as such).  Round 4 wrote the fp16 result and cast it
@@ -857,7 +679,7 @@ int vqs_encode_images(vqs_handle* h, const void* d_pixels, int32_t N, void* d_fe
         g.f16 = psc ? 4 : (p16 ? 2 : 0);
         g.acc_scale = 1.0f / s_mid;
         g.M = NP; g.N = D; g.K = D; g.lda = D; g.ldw = D; g.ldc = D; g.epi = vqs::EPI_BF16;
-        RUN(run_gemm(h, g, st, "mm_projector.2"));
+        VQS_RUN(run_gemm(h, g, st, "mm_projector.2"));
     }
     return VQS_OK;
 }
@@ -878,17 +700,17 @@ static int encoder_pass(vqs_handle* h, const ScoreWs& w, const void* d_feats, co
     const int D = c.d_model, I = h->I, F = c.d_ff, H = c.n_heads, V = c.vocab;
     const int M = B * S, MT = B * T;
     (void)P; (void)M; (void)MT; (void)F; (void)I; (void)V;
-    h->tap_outer = B;
-    GETW(shared, "shared.weight", (int64_t)V * D);
-    GETW(enc_rel, "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", (int64_t)c.rel_buckets * H);
+    h->taps.outer = B;
+    VQS_W(shared, "shared.weight", (int64_t)V * D);
+    VQS_W(enc_rel, "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", (int64_t)c.rel_buckets * H);
 
-    HIPCHK(h, hipMemsetAsync(w.flags, 0, 4 * sizeof(int), st), "memset flags");
-    HIPCHK(h, vqs::launch_prompt_scan(d_input_ids, B, L, P, w.sent_pos, w.enc_len, w.flags, st), "prompt_scan");
-    HIPCHK(h, vqs::launch_relpos_table(enc_rel, h->lut_bidir, h->lut_causal, h->lut_len, c.rel_buckets, w.enc_table, H, S,
+    VQS_HIP(h, hipMemsetAsync(w.flags, 0, 4 * sizeof(int), st), "memset flags");
+    VQS_HIP(h, vqs::launch_prompt_scan(d_input_ids, B, L, P, w.sent_pos, w.enc_len, w.flags, st), "prompt_scan");
+    VQS_HIP(h, vqs::launch_relpos_table(enc_rel, h->lut_bidir, h->lut_causal, h->lut_len, c.rel_buckets, w.enc_table, H, S,
                                        nullptr, 1, st), "encoder bias table");
-    HIPCHK(h, vqs::launch_embed_splice(d_input_ids, w.sent_pos, w.enc_len, d_img_index, shared, (const bf16_t*)d_feats,
+    VQS_HIP(h, vqs::launch_embed_splice(d_input_ids, w.sent_pos, w.enc_len, d_img_index, shared, (const bf16_t*)d_feats,
                                        w.hidden, B, L, P, D, V, st), "embed_splice");
-    TAP("enc", -1, "emb", w.hidden, (size_t)M * D);
+    VQS_TAP("enc", -1, "emb", w.hidden, (size_t)M * D);
 
     // ---------------- encoder (same pending-delta protocol as the vision tower)
     // Fused residual + RMSNorm (VQS_FUSED_NORM=1, off by default): the o / wo GEMM epilogue updates the fp32 stream in
@@ -922,19 +744,19 @@ static int encoder_pass(vqs_handle* h, const ScoreWs& w, const void* d_feats, co
     };
     for (int i = 0; i < c.enc_layers; ++i) {
         const std::string p = "encoder.block." + std::to_string(i) + ".";
-        GETW(ln0, p + "layer.0.layer_norm.weight", D);
-        GETW(ow, p + "layer.0.SelfAttention.o.weight", (int64_t)D * I);
-        GETW(ln1, p + "layer.1.layer_norm.weight", D);
-        GETW(wo, p + "layer.1.DenseReluDense.wo.weight", (int64_t)D * F);
+        VQS_W(ln0, p + "layer.0.layer_norm.weight", D);
+        VQS_W(ow, p + "layer.0.SelfAttention.o.weight", (int64_t)D * I);
+        VQS_W(ln1, p + "layer.1.layer_norm.weight", D);
+        VQS_W(wo, p + "layer.1.DenseReluDense.wo.weight", (int64_t)D * F);
         if (!scaled) {
             if (pend_attn)
-                HIPCHK(h, vqs::launch_rmsnorm(w.hidden, pend_attn, ln0, w.xn, M, D, c.t5_ln_eps, st, pend, true, 0, e16a), "enc rmsnorm0");
+                VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, pend_attn, ln0, w.xn, M, D, c.t5_ln_eps, st, pend, true, 0, e16a), "enc rmsnorm0");
             else
-                HIPCHK(h, vqs::launch_rmsnorm(w.hidden, pend, ln0, w.xn, M, D, c.t5_ln_eps, st, nullptr, true, 0, e16a), "enc rmsnorm0");
+                VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, pend, ln0, w.xn, M, D, c.t5_ln_eps, st, nullptr, true, 0, e16a), "enc rmsnorm0");
             pend = nullptr;
             pend_attn = nullptr;
         }
-        TAP("enc", i, "xn0", w.xn, (size_t)M * D);
+        VQS_TAP("enc", i, "xn0", w.xn, (size_t)M * D);
         {
             GemmCall g{w.xn, e16a ? h->enc_qkv16[i] : h->enc_qkv[i], nullptr};
             g.M = M; g.N = 3 * I; g.K = D; g.lda = D; g.ldw = D; g.ldc = 0; g.epi = vqs::EPI_HEADS;
@@ -942,69 +764,69 @@ static int encoder_pass(vqs_handle* h, const ScoreWs& w, const void* d_feats, co
             g.heads[0] = w.q; g.heads[1] = w.k; g.heads[2] = w.v;
             g.f16 = e16a ? 1 : 0;
             consume(g);
-            RUN(run_gemm(h, g, st, "enc qkv"));
+            VQS_RUN(run_gemm(h, g, st, "enc qkv"));
         }
         {
             vqs::AttnParams a{w.q, w.k, w.v, w.attn, w.enc_table, w.enc_len, B, H, S, 1.0f};
             a.f16 = e16a ? 1 : 0;
-            TAP("enc", i, "q", w.q, (size_t)M * I);
-            TAP("enc", i, "k", w.k, (size_t)M * I);
-            TAP("enc", i, "v", w.v, (size_t)M * I);
-            HIPCHK(h, vqs::launch_attention(a, st), "enc attention");
-            TAP("enc", i, "attn", w.attn, (size_t)M * I);
+            VQS_TAP("enc", i, "q", w.q, (size_t)M * I);
+            VQS_TAP("enc", i, "k", w.k, (size_t)M * I);
+            VQS_TAP("enc", i, "v", w.v, (size_t)M * I);
+            VQS_HIP(h, vqs::launch_attention(a, st), "enc attention");
+            VQS_TAP("enc", i, "attn", w.attn, (size_t)M * I);
         }
         {
             GemmCall g{w.attn, e16a ? h->enc_o16[i] : ow, w.delta};
             g.M = M; g.N = D; g.K = I; g.lda = I; g.ldw = I; g.ldc = D; g.epi = vqs::EPI_BF16;
             g.f16 = e16a ? 2 : 0;                // fp16 operands, bf16 delta
             if (fused) produce(g, ln1);
-            RUN(run_gemm(h, g, st, "enc o"));
-            if (!fused) TAP("enc", i, "d_attn", w.delta, (size_t)M * D);
-            if (fused) HIPCHK(h, vqs::launch_rowss_to_rs(w.rowss, parts, M, 1.0f / (float)D, c.t5_ln_eps, w.rs, st), "row 1/rms");
+            VQS_RUN(run_gemm(h, g, st, "enc o"));
+            if (!fused) VQS_TAP("enc", i, "d_attn", w.delta, (size_t)M * D);
+            if (fused) VQS_HIP(h, vqs::launch_rowss_to_rs(w.rowss, parts, M, 1.0f / (float)D, c.t5_ln_eps, w.rs, st), "row 1/rms");
         }
         if (fused) {
             scaled = true;
         } else {
-            HIPCHK(h, vqs::launch_rmsnorm(w.hidden, w.delta, ln1, w.xn, M, D, c.t5_ln_eps, st, nullptr, !defer, 0, e16f), "enc rmsnorm1");
+            VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, w.delta, ln1, w.xn, M, D, c.t5_ln_eps, st, nullptr, !defer, 0, e16f), "enc rmsnorm1");
             if (defer) pend_attn = w.delta;
             scaled = false;
-            TAP("enc", i, "xn1", w.xn, (size_t)M * D);
+            VQS_TAP("enc", i, "xn1", w.xn, (size_t)M * D);
         }
         {
             GemmCall g{w.xn, e16f ? h->enc_wi16[i] : h->enc_wi[i], w.ff};
             g.M = M; g.N = 2 * F; g.K = D; g.lda = D; g.ldw = D; g.ldc = F; g.epi = vqs::EPI_GATED;
             g.f16 = e16f ? 2 : 0;                // fp16 operands, bf16 gated product
             consume(g);
-            RUN(run_gemm(h, g, st, "enc wi"));
-            TAP("enc", i, "ff", w.ff, (size_t)M * F);
+            VQS_RUN(run_gemm(h, g, st, "enc wi"));
+            VQS_TAP("enc", i, "ff", w.ff, (size_t)M * F);
         }
         {
             bf16_t* dst = defer ? w.delta2 : w.delta;
             GemmCall g{w.ff, wo, dst};
             g.M = M; g.N = D; g.K = F; g.lda = F; g.ldw = F; g.ldc = D; g.epi = vqs::EPI_BF16;
             if (fused && i + 1 < c.enc_layers) {
-                GETW(ln0_next, "encoder.block." + std::to_string(i + 1) + ".layer.0.layer_norm.weight", D);
+                VQS_W(ln0_next, "encoder.block." + std::to_string(i + 1) + ".layer.0.layer_norm.weight", D);
                 produce(g, ln0_next);
-                RUN(run_gemm(h, g, st, "enc wo"));
-                HIPCHK(h, vqs::launch_rowss_to_rs(w.rowss, parts, M, 1.0f / (float)D, c.t5_ln_eps, w.rs, st), "row 1/rms");
+                VQS_RUN(run_gemm(h, g, st, "enc wo"));
+                VQS_HIP(h, vqs::launch_rowss_to_rs(w.rowss, parts, M, 1.0f / (float)D, c.t5_ln_eps, w.rs, st), "row 1/rms");
                 scaled = true;
                 pend = nullptr;
             } else {
-                RUN(run_gemm(h, g, st, "enc wo"));
-                TAP("enc", i, "d_ff", dst, (size_t)M * D);
+                VQS_RUN(run_gemm(h, g, st, "enc wo"));
+                VQS_TAP("enc", i, "d_ff", dst, (size_t)M * D);
                 scaled = false;
                 pend = dst;
             }
         }
     }
     {
-        GETW(fin, "encoder.final_layer_norm.weight", D);
+        VQS_W(fin, "encoder.final_layer_norm.weight", D);
         if (pend_attn)
-            HIPCHK(h, vqs::launch_rmsnorm(w.hidden, pend_attn, fin, w.enc_out, M, D, c.t5_ln_eps, st, pend, true, 0, e_out_f16), "enc final norm");
+            VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, pend_attn, fin, w.enc_out, M, D, c.t5_ln_eps, st, pend, true, 0, e_out_f16), "enc final norm");
         else
-            HIPCHK(h, vqs::launch_rmsnorm(w.hidden, pend, fin, w.enc_out, M, D, c.t5_ln_eps, st, nullptr, true, 0, e_out_f16), "enc final norm");
+            VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, pend, fin, w.enc_out, M, D, c.t5_ln_eps, st, nullptr, true, 0, e_out_f16), "enc final norm");
         if (h->cross_mode != 0)
-            HIPCHK(h, vqs::launch_transpose_pad(w.enc_out, w.enc_outT, B, S, D, w.S_pad, st), "enc_out transpose");
+            VQS_HIP(h, vqs::launch_transpose_pad(w.enc_out, w.enc_outT, B, S, D, w.S_pad, st), "enc_out transpose");
     }
 
     return VQS_OK;
@@ -1038,8 +860,8 @@ static int dec_linear(vqs_handle* h, const bf16_t* A, const bf16_t* W, bf16_t* o
         GemmCall g{A, W, scratch};
         g.M = MT; g.N = N; g.K = K / sk; g.lda = K; g.ldw = K; g.ldc = N; g.epi = vqs::EPI_F32;
         g.batch = sk; g.sA = K / sk; g.sW = K / sk; g.sC = (long long)MT * N;
-        RUN(run_gemm(h, g, st, what));
-        HIPCHK(h, vqs::launch_reduce_slices(scratch, sk, (size_t)MT * N, out, st), "split-K reduce");
+        VQS_RUN(run_gemm(h, g, st, what));
+        VQS_HIP(h, vqs::launch_reduce_slices(scratch, sk, (size_t)MT * N, out, st), "split-K reduce");
         return VQS_OK;
     }
     GemmCall g{A, W, out};
@@ -1058,8 +880,8 @@ static int dec_linear_split(vqs_handle* h, const bf16_t* A2, const bf16_t* W, in
     GemmCall g{A2, W, scratch};
     g.M = 2 * MT; g.N = N; g.K = K / sk; g.lda = K; g.ldw = K; g.ldc = N; g.epi = vqs::EPI_F32;
     g.batch = sk; g.sA = K / sk; g.sW = K / sk; g.sC = (long long)2 * MT * N;
-    RUN(run_gemm(h, g, st, what));
-    HIPCHK(h, vqs::launch_sum_planes(scratch, sk, (long long)2 * MT * N, MT, N, N, mode, out, ld_out, out_plane, st), "sum of stacked partials");
+    VQS_RUN(run_gemm(h, g, st, what));
+    VQS_HIP(h, vqs::launch_sum_planes(scratch, sk, (long long)2 * MT * N, MT, N, N, mode, out, ld_out, out_plane, st), "sum of stacked partials");
     return VQS_OK;
 }
 
@@ -1074,58 +896,58 @@ static int decoder_pass(vqs_handle* h, const ScoreWs& w, const int32_t* d_labels
     const int D = c.d_model, I = h->I, F = c.d_ff, H = c.n_heads, V = c.vocab;
     const int M = B * S, MT = B * T;
     (void)P; (void)M; (void)MT; (void)F; (void)I; (void)V;
-    h->tap_outer = B;
+    h->taps.outer = B;
     // ---------------- decoder (teacher forced, T rows per pair)
-    GETW(shared, "shared.weight", (int64_t)V * D);
+    VQS_W(shared, "shared.weight", (int64_t)V * D);
     float* scratch = w.dscratch;
     const size_t scratch_bytes = w.dscratch_bytes;
-    GETW(dec_rel, "decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", (int64_t)c.rel_buckets * H);
+    VQS_W(dec_rel, "decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", (int64_t)c.rel_buckets * H);
     const int TB = cached ? w.Tc : T;                          // row length of the decoder bias table
     if (!cached || pos0 == 0)
-        HIPCHK(h, vqs::launch_relpos_table(dec_rel, h->lut_bidir, h->lut_causal, h->lut_len, c.rel_buckets, nullptr, H, S,
+        VQS_HIP(h, vqs::launch_relpos_table(dec_rel, h->lut_bidir, h->lut_causal, h->lut_len, c.rel_buckets, nullptr, H, S,
                                            w.dec_table, TB, st), "decoder bias table");
-    HIPCHK(h, vqs::launch_decoder_embed(d_labels, ld_labels, shared, w.dhid, B, T, D, V, st, pos0), "decoder embed");
-    TAP("dec", -1, "emb", w.dhid, (size_t)MT * D);
+    VQS_HIP(h, vqs::launch_decoder_embed(d_labels, ld_labels, shared, w.dhid, B, T, D, V, st, pos0), "decoder embed");
+    VQS_TAP("dec", -1, "emb", w.dhid, (size_t)MT * D);
     const bf16_t* dpend = nullptr;
     for (int i = 0; i < c.dec_layers; ++i) {
         const std::string p = "decoder.block." + std::to_string(i) + ".";
-        GETW(ln0, p + "layer.0.layer_norm.weight", D);
-        GETW(so, p + "layer.0.SelfAttention.o.weight", (int64_t)D * I);
-        GETW(ln1, p + "layer.1.layer_norm.weight", D);
-        GETW(cq, p + "layer.1.EncDecAttention.q.weight", (int64_t)I * D);
-        GETW(co, p + "layer.1.EncDecAttention.o.weight", (int64_t)D * I);
-        GETW(ln2, p + "layer.2.layer_norm.weight", D);
-        GETW(wo, p + "layer.2.DenseReluDense.wo.weight", (int64_t)D * F);
+        VQS_W(ln0, p + "layer.0.layer_norm.weight", D);
+        VQS_W(so, p + "layer.0.SelfAttention.o.weight", (int64_t)D * I);
+        VQS_W(ln1, p + "layer.1.layer_norm.weight", D);
+        VQS_W(cq, p + "layer.1.EncDecAttention.q.weight", (int64_t)I * D);
+        VQS_W(co, p + "layer.1.EncDecAttention.o.weight", (int64_t)D * I);
+        VQS_W(ln2, p + "layer.2.layer_norm.weight", D);
+        VQS_W(wo, p + "layer.2.DenseReluDense.wo.weight", (int64_t)D * F);
 
-        HIPCHK(h, vqs::launch_rmsnorm(w.dhid, dpend, ln0, w.dxn, MT, D, c.t5_ln_eps, st), "dec rmsnorm0");
+        VQS_HIP(h, vqs::launch_rmsnorm(w.dhid, dpend, ln0, w.dxn, MT, D, c.t5_ln_eps, st), "dec rmsnorm0");
         dpend = nullptr;
-        TAP("dec", i, "xn0", w.dxn, (size_t)MT * D);
-        RUN(dec_linear(h, w.dxn, h->dec_qkv[i], w.dqkv, MT, 3 * I, D, scratch, scratch_bytes, st, "dec self qkv"));
-        TAP("dec", i, "qkv", w.dqkv, (size_t)MT * 3 * I);
+        VQS_TAP("dec", i, "xn0", w.dxn, (size_t)MT * D);
+        VQS_RUN(dec_linear(h, w.dxn, h->dec_qkv[i], w.dqkv, MT, 3 * I, D, scratch, scratch_bytes, st, "dec self qkv"));
+        VQS_TAP("dec", i, "qkv", w.dqkv, (size_t)MT * 3 * I);
         if (cached) {
             // append this step's k | v rows (columns I .. 3I of dqkv) to layer i's cache at position pos0, then attend over
             // positions 0 .. pos0+T-1 of the cache
             bf16_t* cl = w.kvcache + (size_t)i * B * w.Tc * 2 * I;
-            HIPCHK(h, hipMemcpy2DAsync(cl + (size_t)pos0 * 2 * I, (size_t)w.Tc * 2 * I * sizeof(bf16_t), w.dqkv + I,
+            VQS_HIP(h, hipMemcpy2DAsync(cl + (size_t)pos0 * 2 * I, (size_t)w.Tc * 2 * I * sizeof(bf16_t), w.dqkv + I,
                                        (size_t)3 * I * sizeof(bf16_t), (size_t)2 * I * sizeof(bf16_t) * T, B,
                                        hipMemcpyDeviceToDevice, st), "kv cache append");
             vqs::DecAttnParams a{w.dqkv, cl, cl + I, w.dattn, w.dec_table, nullptr, B, H, T, pos0 + T, 3 * I, 2 * I, 0};
             a.kv_stride_b = (long long)w.Tc * 2 * I;
             a.qpos0 = pos0;
             a.bias_ld = TB;
-            HIPCHK(h, vqs::launch_decoder_attention(a, st), "dec self attention (cached)");
-            TAP("dec", i, "sattn", w.dattn, (size_t)MT * I);
+            VQS_HIP(h, vqs::launch_decoder_attention(a, st), "dec self attention (cached)");
+            VQS_TAP("dec", i, "sattn", w.dattn, (size_t)MT * I);
         } else {
             vqs::DecAttnParams a{w.dqkv, w.dqkv + I, w.dqkv + 2 * I, w.dattn, w.dec_table, nullptr, B, H, T, T, 3 * I, 3 * I, 0};
-            HIPCHK(h, vqs::launch_decoder_attention(a, st), "dec self attention");
-            TAP("dec", i, "sattn", w.dattn, (size_t)MT * I);
+            VQS_HIP(h, vqs::launch_decoder_attention(a, st), "dec self attention");
+            VQS_TAP("dec", i, "sattn", w.dattn, (size_t)MT * I);
         }
-        RUN(dec_linear(h, w.dattn, so, w.ddelta, MT, D, I, scratch, scratch_bytes, st, "dec self o"));
-        TAP("dec", i, "d_self", w.ddelta, (size_t)MT * D);
-        HIPCHK(h, vqs::launch_rmsnorm(w.dhid, w.ddelta, ln1, w.dxn, MT, D, c.t5_ln_eps, st), "dec rmsnorm1");
-        TAP("dec", i, "xn1", w.dxn, (size_t)MT * D);
-        RUN(dec_linear(h, w.dxn, cq, w.dq, MT, I, D, scratch, scratch_bytes, st, "dec cross q"));
-        TAP("dec", i, "cq", w.dq, (size_t)MT * I);
+        VQS_RUN(dec_linear(h, w.dattn, so, w.ddelta, MT, D, I, scratch, scratch_bytes, st, "dec self o"));
+        VQS_TAP("dec", i, "d_self", w.ddelta, (size_t)MT * D);
+        VQS_HIP(h, vqs::launch_rmsnorm(w.dhid, w.ddelta, ln1, w.dxn, MT, D, c.t5_ln_eps, st), "dec rmsnorm1");
+        VQS_TAP("dec", i, "xn1", w.dxn, (size_t)MT * D);
+        VQS_RUN(dec_linear(h, w.dxn, cq, w.dq, MT, I, D, scratch, scratch_bytes, st, "dec cross q"));
+        VQS_TAP("dec", i, "cq", w.dq, (size_t)MT * I);
         if (h->cross_mode == 0) {
             // direct form (what HF executes): K|V projection of the whole encoder output for this layer
             {
@@ -1133,71 +955,71 @@ static int decoder_pass(vqs_handle* h, const ScoreWs& w, const int32_t* d_labels
                 g.M = M; g.N = 2 * I; g.K = D; g.lda = D; g.ldw = D; g.ldc = 0; g.epi = vqs::EPI_HEADS;
                 g.S = S; g.H = H; g.inner = I;
                 g.heads[0] = w.ck; g.heads[1] = w.cv; g.heads[2] = nullptr;
-                RUN(run_gemm(h, g, st, "dec cross kv"));
+                VQS_RUN(run_gemm(h, g, st, "dec cross kv"));
             }
             vqs::DecAttnParams a{w.dq, w.ck, w.cv, w.dattn, nullptr, w.enc_len, B, H, T, S, I, 0, 1};
-            HIPCHK(h, vqs::launch_decoder_attention(a, st), "dec cross attention");
+            VQS_HIP(h, vqs::launch_decoder_attention(a, st), "dec cross attention");
         } else {
             // Reassociated cross-attention.  With E = encoder output [S,D] and T (<=16) decoder rows per pair,
             //   scores_h = q_h (E Wk_h^T)^T = (q_h Wk_h) E^T          and       out_h = P_h (E Wv_h^T) = (P_h E) Wv_h^T,
             // so the per-layer [B*S, D] x [D, 2I] projection (4*S*D*I FLOPs per pair and layer, 98 % of the decoder)
             // becomes five small batched GEMMs over E itself (~30x fewer FLOPs); same function, fp32 accumulation.
-            GETW(cv_w, p + "layer.1.EncDecAttention.v.weight", (int64_t)I * D);
+            VQS_W(cv_w, p + "layer.1.EncDecAttention.v.weight", (int64_t)I * D);
             const int R = T * H;        // rows per pair, ordered (t, h)
             {   // q'[(b,t), h, :] = q[(b,t), h*64:(h+1)*64] . Wk_h            batched over heads
                 GemmCall g{w.dq, h->dec_ckT[i], w.cqk};
                 g.M = MT; g.N = D; g.K = 64; g.lda = I; g.ldw = I; g.ldc = H * D; g.epi = vqs::EPI_BF16;
                 g.batch = H; g.sA = 64; g.sW = 64; g.sC = D;
-                RUN(run_gemm(h, g, st, "cross q.Wk"));
-                TAP("dec", i, "cqk", w.cqk, (size_t)MT * H * D);
+                VQS_RUN(run_gemm(h, g, st, "cross q.Wk"));
+                VQS_TAP("dec", i, "cqk", w.cqk, (size_t)MT * H * D);
             }
             {   // scores[b] [R, S] = q'[b] [R, D] . E[b]^T                      batched over pairs
                 GemmCall g{w.cqk, w.enc_out, w.cscores};
                 g.M = R; g.N = S; g.K = D; g.lda = D; g.ldw = D; g.ldc = w.S_pad; g.epi = vqs::EPI_F32;
                 g.batch = B; g.sA = (long long)R * D; g.sW = (long long)S * D; g.sC = (long long)R * w.S_pad;
-                RUN(run_gemm(h, g, st, "cross scores"));
-                TAP("dec", i, "cscores", w.cscores, (size_t)MT * H * w.S_pad);
+                VQS_RUN(run_gemm(h, g, st, "cross scores"));
+                VQS_TAP("dec", i, "cscores", w.cscores, (size_t)MT * H * w.S_pad);
             }
-            HIPCHK(h, vqs::launch_masked_softmax(w.cscores, w.cprobs, w.enc_len, B, R, w.S_pad, st), "cross softmax");
-            TAP("dec", i, "cprobs", w.cprobs, (size_t)MT * H * w.S_pad);
+            VQS_HIP(h, vqs::launch_masked_softmax(w.cscores, w.cprobs, w.enc_len, B, R, w.S_pad, st), "cross softmax");
+            VQS_TAP("dec", i, "cprobs", w.cprobs, (size_t)MT * H * w.S_pad);
             {   // ctx[b] [R, D] = P[b] [R, S_pad] . E[b]  (E^T is K-contiguous)   batched over pairs
                 GemmCall g{w.cprobs, w.enc_outT, w.cctx};
                 g.M = R; g.N = D; g.K = w.S_pad; g.lda = w.S_pad; g.ldw = w.S_pad; g.ldc = D; g.epi = vqs::EPI_BF16;
                 g.batch = B; g.sA = (long long)R * w.S_pad; g.sW = (long long)D * w.S_pad; g.sC = (long long)R * D;
                 g.no_stream = 1;      // K = S_pad = 640: ten slabs per item -- the stream form's pipeline fill per item costs more than its
                                   // deeper ring gains (0.50 vs 0.41 ms per launch, profiles/r4_call4_*); the scores launch (K = D) streams
-            RUN(run_gemm(h, g, st, "cross P.E"));
-                TAP("dec", i, "cctx", w.cctx, (size_t)MT * H * D);
+            VQS_RUN(run_gemm(h, g, st, "cross P.E"));
+                VQS_TAP("dec", i, "cctx", w.cctx, (size_t)MT * H * D);
             }
             {   // out[(b,t), h*64:(h+1)*64] = ctx[(b,t), h, :] . Wv_h^T          batched over heads
                 GemmCall g{w.cctx, cv_w, w.dattn};
                 g.M = MT; g.N = 64; g.K = D; g.lda = H * D; g.ldw = D; g.ldc = I; g.epi = vqs::EPI_BF16;
                 g.batch = H; g.sA = D; g.sW = (long long)64 * D; g.sC = 64;
-                RUN(run_gemm(h, g, st, "cross ctx.Wv"));
+                VQS_RUN(run_gemm(h, g, st, "cross ctx.Wv"));
             }
         }
-        TAP("dec", i, "cattn", w.dattn, (size_t)MT * I);
-        RUN(dec_linear(h, w.dattn, co, w.ddelta, MT, D, I, scratch, scratch_bytes, st, "dec cross o"));
-        TAP("dec", i, "d_cross", w.ddelta, (size_t)MT * D);
-        HIPCHK(h, vqs::launch_rmsnorm(w.dhid, w.ddelta, ln2, w.dxn, MT, D, c.t5_ln_eps, st), "dec rmsnorm2");
-        TAP("dec", i, "xn2", w.dxn, (size_t)MT * D);
+        VQS_TAP("dec", i, "cattn", w.dattn, (size_t)MT * I);
+        VQS_RUN(dec_linear(h, w.dattn, co, w.ddelta, MT, D, I, scratch, scratch_bytes, st, "dec cross o"));
+        VQS_TAP("dec", i, "d_cross", w.ddelta, (size_t)MT * D);
+        VQS_HIP(h, vqs::launch_rmsnorm(w.dhid, w.ddelta, ln2, w.dxn, MT, D, c.t5_ln_eps, st), "dec rmsnorm2");
+        VQS_TAP("dec", i, "xn2", w.dxn, (size_t)MT * D);
         {
             GemmCall g{w.dxn, h->dec_wi[i], w.dff};
             g.M = MT; g.N = 2 * F; g.K = D; g.lda = D; g.ldw = D; g.ldc = F; g.epi = vqs::EPI_GATED;
-            RUN(run_gemm(h, g, st, "dec wi"));
-            TAP("dec", i, "ff", w.dff, (size_t)MT * F);
+            VQS_RUN(run_gemm(h, g, st, "dec wi"));
+            VQS_TAP("dec", i, "ff", w.dff, (size_t)MT * F);
         }
-        RUN(dec_linear(h, w.dff, wo, w.ddelta, MT, D, F, scratch, scratch_bytes, st, "dec wo"));
-        TAP("dec", i, "d_ff", w.ddelta, (size_t)MT * D);
+        VQS_RUN(dec_linear(h, w.dff, wo, w.ddelta, MT, D, F, scratch, scratch_bytes, st, "dec wo"));
+        VQS_TAP("dec", i, "d_ff", w.ddelta, (size_t)MT * D);
         dpend = w.ddelta;
     }
     {
-        GETW(fin, "decoder.final_layer_norm.weight", D);
-        GETW(head, "lm_head.weight", (int64_t)V * D);
-        HIPCHK(h, vqs::launch_rmsnorm(w.dhid, dpend, fin, w.dxn, MT, D, c.t5_ln_eps, st), "dec final norm");
+        VQS_W(fin, "decoder.final_layer_norm.weight", D);
+        VQS_W(head, "lm_head.weight", (int64_t)V * D);
+        VQS_HIP(h, vqs::launch_rmsnorm(w.dhid, dpend, fin, w.dxn, MT, D, c.t5_ln_eps, st), "dec final norm");
         GemmCall g{w.dxn, head, w.logits};
         g.M = MT; g.N = V; g.K = D; g.lda = D; g.ldw = D; g.ldc = w.ldl; g.epi = vqs::EPI_F32;
-        RUN(run_gemm(h, g, st, "lm_head"));
+        VQS_RUN(run_gemm(h, g, st, "lm_head"));
     }
     return VQS_OK;
 }
@@ -1217,72 +1039,72 @@ static int decoder_pass_precise(vqs_handle* h, const ScoreWs& w, const int32_t* 
     const int P = h->P, S = L - 1 + P;
     const int D = c.d_model, I = h->I, F = c.d_ff, H = c.n_heads, V = c.vocab;
     const int MT = B * T;
-    h->tap_outer = B;
-    GETW(shared, "shared.weight", (int64_t)V * D);
-    GETW(dec_rel, "decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", (int64_t)c.rel_buckets * H);
+    h->taps.outer = B;
+    VQS_W(shared, "shared.weight", (int64_t)V * D);
+    VQS_W(dec_rel, "decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", (int64_t)c.rel_buckets * H);
     float* scratch = w.dscratch;
     const size_t sb = w.dscratch_bytes;
     const long long pD = (long long)MT * D, pI = (long long)MT * I, pF = (long long)MT * F, pC = (long long)MT * H * D;   // plane sizes
-    HIPCHK(h, vqs::launch_relpos_table(dec_rel, h->lut_bidir, h->lut_causal, h->lut_len, c.rel_buckets, nullptr, H, S, w.dec_table, T, st),
+    VQS_HIP(h, vqs::launch_relpos_table(dec_rel, h->lut_bidir, h->lut_causal, h->lut_len, c.rel_buckets, nullptr, H, S, w.dec_table, T, st),
            "decoder bias table");
-    HIPCHK(h, vqs::launch_decoder_embed(d_labels, ld_labels, shared, w.dhid, B, T, D, V, st, 0), "decoder embed");
-    TAP("dec", -1, "emb", w.dhid, (size_t)MT * D);
+    VQS_HIP(h, vqs::launch_decoder_embed(d_labels, ld_labels, shared, w.dhid, B, T, D, V, st, 0), "decoder embed");
+    VQS_TAP("dec", -1, "emb", w.dhid, (size_t)MT * D);
     const float* dpend = nullptr;
     for (int i = 0; i < c.dec_layers; ++i) {
         const std::string p = "decoder.block." + std::to_string(i) + ".";
-        GETW(ln0, p + "layer.0.layer_norm.weight", D);
-        GETW(so, p + "layer.0.SelfAttention.o.weight", (int64_t)D * I);
-        GETW(ln1, p + "layer.1.layer_norm.weight", D);
-        GETW(cq, p + "layer.1.EncDecAttention.q.weight", (int64_t)I * D);
-        GETW(cv_w, p + "layer.1.EncDecAttention.v.weight", (int64_t)I * D);
-        GETW(co, p + "layer.1.EncDecAttention.o.weight", (int64_t)D * I);
-        GETW(ln2, p + "layer.2.layer_norm.weight", D);
-        GETW(wo, p + "layer.2.DenseReluDense.wo.weight", (int64_t)D * F);
+        VQS_W(ln0, p + "layer.0.layer_norm.weight", D);
+        VQS_W(so, p + "layer.0.SelfAttention.o.weight", (int64_t)D * I);
+        VQS_W(ln1, p + "layer.1.layer_norm.weight", D);
+        VQS_W(cq, p + "layer.1.EncDecAttention.q.weight", (int64_t)I * D);
+        VQS_W(cv_w, p + "layer.1.EncDecAttention.v.weight", (int64_t)I * D);
+        VQS_W(co, p + "layer.1.EncDecAttention.o.weight", (int64_t)D * I);
+        VQS_W(ln2, p + "layer.2.layer_norm.weight", D);
+        VQS_W(wo, p + "layer.2.DenseReluDense.wo.weight", (int64_t)D * F);
 
         // ---- causal self-attention
-        HIPCHK(h, vqs::launch_rmsnorm_split(w.dhid, dpend, ln0, w.dxn, pD, MT, D, c.t5_ln_eps, st), "dec rmsnorm0");
+        VQS_HIP(h, vqs::launch_rmsnorm_split(w.dhid, dpend, ln0, w.dxn, pD, MT, D, c.t5_ln_eps, st), "dec rmsnorm0");
         dpend = nullptr;
         TAP2("dec", i, "xn0", w.dxn, pD);
-        RUN(dec_linear_split(h, w.dxn, h->dec_qkv[i], MT, 3 * I, D, scratch, sb, vqs::SUM_F32, w.dqkv32, 3 * I, 0, st, "dec self qkv"));
-        TAP("dec", i, "qkv", w.dqkv32, (size_t)MT * 3 * I);
+        VQS_RUN(dec_linear_split(h, w.dxn, h->dec_qkv[i], MT, 3 * I, D, scratch, sb, vqs::SUM_F32, w.dqkv32, 3 * I, 0, st, "dec self qkv"));
+        VQS_TAP("dec", i, "qkv", w.dqkv32, (size_t)MT * 3 * I);
         {
             vqs::DecAttnParams a{reinterpret_cast<const bf16_t*>(w.dqkv32), reinterpret_cast<const bf16_t*>(w.dqkv32 + I),
                                  reinterpret_cast<const bf16_t*>(w.dqkv32 + 2 * I), w.dattn, w.dec_table, nullptr, B, H, T, T, 3 * I, 3 * I, 0};
             a.precise = 1;
             a.out_plane = pI;
-            HIPCHK(h, vqs::launch_decoder_attention(a, st), "dec self attention");
+            VQS_HIP(h, vqs::launch_decoder_attention(a, st), "dec self attention");
         }
         TAP2("dec", i, "sattn", w.dattn, pI);
-        RUN(dec_linear_split(h, w.dattn, so, MT, D, I, scratch, sb, vqs::SUM_F32, w.ddelta32, D, 0, st, "dec self o"));
-        TAP("dec", i, "d_self", w.ddelta32, (size_t)MT * D);
+        VQS_RUN(dec_linear_split(h, w.dattn, so, MT, D, I, scratch, sb, vqs::SUM_F32, w.ddelta32, D, 0, st, "dec self o"));
+        VQS_TAP("dec", i, "d_self", w.ddelta32, (size_t)MT * D);
         // ---- cross-attention (reassociated, vqs_api.cpp decoder_pass): score path in bf16 off the hi plane, value path precise
-        HIPCHK(h, vqs::launch_rmsnorm_split(w.dhid, w.ddelta32, ln1, w.dxn, pD, MT, D, c.t5_ln_eps, st), "dec rmsnorm1");
+        VQS_HIP(h, vqs::launch_rmsnorm_split(w.dhid, w.ddelta32, ln1, w.dxn, pD, MT, D, c.t5_ln_eps, st), "dec rmsnorm1");
         TAP2("dec", i, "xn1", w.dxn, pD);
         // option dec_fp16 (x16): q from BOTH planes of the split norm output, rounded once to fp16; q.Wk, the probabilities and E are fp16 tensors
         if (x16)
-            RUN(dec_linear_split(h, w.dxn, cq, MT, I, D, scratch, sb, vqs::SUM_F16, w.dq, I, 0, st, "dec cross q"));
+            VQS_RUN(dec_linear_split(h, w.dxn, cq, MT, I, D, scratch, sb, vqs::SUM_F16, w.dq, I, 0, st, "dec cross q"));
         else
-            RUN(dec_linear(h, w.dxn, cq, w.dq, MT, I, D, scratch, sb, st, "dec cross q"));
-        TAP("dec", i, "cq", w.dq, (size_t)MT * I);
+            VQS_RUN(dec_linear(h, w.dxn, cq, w.dq, MT, I, D, scratch, sb, st, "dec cross q"));
+        VQS_TAP("dec", i, "cq", w.dq, (size_t)MT * I);
         const int R = T * H;        // rows per pair, ordered (t, h)
         {   // q'[(b,t), h, :] = q[(b,t), h*64:(h+1)*64] . Wk_h            batched over heads
             GemmCall g{w.dq, x16 ? h->dec_ckT16[i] : h->dec_ckT[i], w.cqk};
             g.M = MT; g.N = D; g.K = 64; g.lda = I; g.ldw = I; g.ldc = H * D; g.epi = vqs::EPI_BF16;
             g.batch = H; g.sA = 64; g.sW = 64; g.sC = D;
             g.f16 = x16 ? 1 : 0;
-            RUN(run_gemm(h, g, st, "cross q.Wk"));
-            TAP("dec", i, "cqk", w.cqk, (size_t)MT * H * D);
+            VQS_RUN(run_gemm(h, g, st, "cross q.Wk"));
+            VQS_TAP("dec", i, "cqk", w.cqk, (size_t)MT * H * D);
         }
         {   // scores[b] [R, S] = q'[b] [R, D] . E[b]^T                      batched over pairs
             GemmCall g{w.cqk, w.enc_out, w.cscores};
             g.M = R; g.N = S; g.K = D; g.lda = D; g.ldw = D; g.ldc = w.S_pad; g.epi = vqs::EPI_F32;
             g.batch = B; g.sA = (long long)R * D; g.sW = (long long)S * D; g.sC = (long long)R * w.S_pad;
             g.f16 = x16 ? 1 : 0;
-            RUN(run_gemm(h, g, st, "cross scores"));
-            TAP("dec", i, "cscores", w.cscores, (size_t)MT * H * w.S_pad);
+            VQS_RUN(run_gemm(h, g, st, "cross scores"));
+            VQS_TAP("dec", i, "cscores", w.cscores, (size_t)MT * H * w.S_pad);
         }
-        HIPCHK(h, vqs::launch_masked_softmax(w.cscores, w.cprobs, w.enc_len, B, R, w.S_pad, st, x16), "cross softmax");
-        TAP("dec", i, "cprobs", w.cprobs, (size_t)MT * H * w.S_pad);
+        VQS_HIP(h, vqs::launch_masked_softmax(w.cscores, w.cprobs, w.enc_len, B, R, w.S_pad, st, x16), "cross softmax");
+        VQS_TAP("dec", i, "cprobs", w.cprobs, (size_t)MT * H * w.S_pad);
         {   // ctx[b] [R, D] = P[b] [R, S_pad] . E[b]   -> split-bf16: hi plane = the tensor of rounds 1-3, lo plane behind it
             GemmCall g{w.cprobs, w.enc_outT, w.cctx};
             g.M = R; g.N = D; g.K = w.S_pad; g.lda = w.S_pad; g.ldw = w.S_pad; g.ldc = D; g.epi = vqs::EPI_BF16;
@@ -1291,7 +1113,7 @@ static int decoder_pass_precise(vqs_handle* h, const ScoreWs& w, const int32_t* 
             g.f16 = x16 ? 2 : 0;          // fp16 operands (P, E^T), split-bf16 result
             g.no_stream = 1;      // K = S_pad = 640: ten slabs per item -- the stream form's pipeline fill per item costs more than its
                                   // deeper ring gains (0.50 vs 0.41 ms per launch, profiles/r4_call4_*); the scores launch (K = D) streams
-            RUN(run_gemm(h, g, st, "cross P.E"));
+            VQS_RUN(run_gemm(h, g, st, "cross P.E"));
             TAP2("dec", i, "cctx", w.cctx, pC);
         }
         {   // out[(b,t), h*64:(h+1)*64] = ctx[(b,t), h, :] . Wv_h^T          batched over heads; both planes as 2*MT stacked rows
@@ -1299,27 +1121,27 @@ static int decoder_pass_precise(vqs_handle* h, const ScoreWs& w, const int32_t* 
             g.M = 2 * MT; g.N = 64; g.K = D; g.lda = H * D; g.ldw = D; g.ldc = I; g.epi = vqs::EPI_F32;
             g.batch = H; g.sA = D; g.sW = (long long)64 * D; g.sC = 64;
             if ((size_t)2 * MT * I * sizeof(float) > sb) return fail(h, VQS_ERR_WORKSPACE, "cross ctx.Wv: decoder scratch too small");
-            RUN(run_gemm(h, g, st, "cross ctx.Wv"));
-            HIPCHK(h, vqs::launch_sum_planes(scratch, 1, 0, MT, I, I, vqs::SUM_SPLIT, w.dattn, I, pI, st), "cross ctx.Wv planes");
+            VQS_RUN(run_gemm(h, g, st, "cross ctx.Wv"));
+            VQS_HIP(h, vqs::launch_sum_planes(scratch, 1, 0, MT, I, I, vqs::SUM_SPLIT, w.dattn, I, pI, st), "cross ctx.Wv planes");
         }
         TAP2("dec", i, "cattn", w.dattn, pI);
-        RUN(dec_linear_split(h, w.dattn, co, MT, D, I, scratch, sb, vqs::SUM_F32, w.ddelta32, D, 0, st, "dec cross o"));
-        TAP("dec", i, "d_cross", w.ddelta32, (size_t)MT * D);
+        VQS_RUN(dec_linear_split(h, w.dattn, co, MT, D, I, scratch, sb, vqs::SUM_F32, w.ddelta32, D, 0, st, "dec cross o"));
+        VQS_TAP("dec", i, "d_cross", w.ddelta32, (size_t)MT * D);
         // ---- gated FFN
-        HIPCHK(h, vqs::launch_rmsnorm_split(w.dhid, w.ddelta32, ln2, w.dxn, pD, MT, D, c.t5_ln_eps, st), "dec rmsnorm2");
+        VQS_HIP(h, vqs::launch_rmsnorm_split(w.dhid, w.ddelta32, ln2, w.dxn, pD, MT, D, c.t5_ln_eps, st), "dec rmsnorm2");
         TAP2("dec", i, "xn2", w.dxn, pD);
-        RUN(dec_linear_split(h, w.dxn, h->dec_wi[i], MT, 2 * F, D, scratch, sb, vqs::SUM_GATED_SPLIT, w.dff, F, pF, st, "dec wi"));
+        VQS_RUN(dec_linear_split(h, w.dxn, h->dec_wi[i], MT, 2 * F, D, scratch, sb, vqs::SUM_GATED_SPLIT, w.dff, F, pF, st, "dec wi"));
         TAP2("dec", i, "ff", w.dff, pF);
-        RUN(dec_linear_split(h, w.dff, wo, MT, D, F, scratch, sb, vqs::SUM_F32, w.ddelta32, D, 0, st, "dec wo"));
-        TAP("dec", i, "d_ff", w.ddelta32, (size_t)MT * D);
+        VQS_RUN(dec_linear_split(h, w.dff, wo, MT, D, F, scratch, sb, vqs::SUM_F32, w.ddelta32, D, 0, st, "dec wo"));
+        VQS_TAP("dec", i, "d_ff", w.ddelta32, (size_t)MT * D);
         dpend = w.ddelta32;
     }
     {
-        GETW(fin, "decoder.final_layer_norm.weight", D);
-        GETW(head, "lm_head.weight", (int64_t)V * D);
-        HIPCHK(h, vqs::launch_rmsnorm_split(w.dhid, dpend, fin, w.dxn, pD, MT, D, c.t5_ln_eps, st), "dec final norm");
+        VQS_W(fin, "decoder.final_layer_norm.weight", D);
+        VQS_W(head, "lm_head.weight", (int64_t)V * D);
+        VQS_HIP(h, vqs::launch_rmsnorm_split(w.dhid, dpend, fin, w.dxn, pD, MT, D, c.t5_ln_eps, st), "dec final norm");
         if ((w.ldl % 4) != 0 || (V % 4) != 0) return fail(h, VQS_ERR_INVALID, "precise decoder: vocabulary must be a multiple of 4");
-        RUN(dec_linear_split(h, w.dxn, head, MT, V, D, scratch, sb, vqs::SUM_F32, w.logits, w.ldl, 0, st, "lm_head"));
+        VQS_RUN(dec_linear_split(h, w.dxn, head, MT, V, D, scratch, sb, vqs::SUM_F32, w.logits, w.ldl, 0, st, "lm_head"));
     }
     return VQS_OK;
 }
@@ -1344,12 +1166,12 @@ int vqs_score(vqs_handle* h, const void* d_feats, const int32_t* d_img_index, co
     const bool precise = h->dec_precise && h->cross_mode != 0;
     if (precise && h->dec_fp16 && h->gemm_variant != 3)
         return fail(h, VQS_ERR_STATE, "score: the fp16 cross-attention score path (option dec_fp16, default 1) needs gemm_variant 3; set dec_fp16=0 to A/B other GEMM forms");
-    RUN(encoder_pass(h, w, d_feats, d_img_index, d_input_ids, B, L, st, precise && h->dec_fp16 != 0));
+    VQS_RUN(encoder_pass(h, w, d_feats, d_img_index, d_input_ids, B, L, st, precise && h->dec_fp16 != 0));
     if (precise)
-        RUN(decoder_pass_precise(h, w, d_labels, T, B, L, T, st));
+        VQS_RUN(decoder_pass_precise(h, w, d_labels, T, B, L, T, st));
     else                                             // bf16 decoder of rounds 1-3 (option dec_precise=0, or the direct cross-attention form)
-        RUN(decoder_pass(h, w, d_labels, T, B, L, T, st));
-    HIPCHK(h, vqs::launch_score_head(w.logits, w.ldl, V, d_labels, d_lp, d_scores, B, T, st, w.flags), "score head");
+        VQS_RUN(decoder_pass(h, w, d_labels, T, B, L, T, st));
+    VQS_HIP(h, vqs::launch_score_head(w.logits, w.ldl, V, d_labels, d_lp, d_scores, B, T, st, w.flags), "score head");
     return VQS_OK;
 }
 
@@ -1377,12 +1199,12 @@ int vqs_generate(vqs_handle* h, const void* d_feats, const int32_t* d_img_index,
     const ScoreWs w = carve_score(h, (char*)d_ws, B, L, 1, nullptr, max_new);
     if (ws_bytes < w.total) return fail(h, VQS_ERR_WORKSPACE, "generate: workspace too small (size it with vqs_generate_workspace_bytes(B, L, max_new))");
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(h, hipMemsetAsync(d_tokens, 0, (size_t)B * max_new * sizeof(int32_t), st), "memset tokens");
-    RUN(encoder_pass(h, w, d_feats, d_img_index, d_input_ids, B, L, st));
+    VQS_HIP(h, hipMemsetAsync(d_tokens, 0, (size_t)B * max_new * sizeof(int32_t), st), "memset tokens");
+    VQS_RUN(encoder_pass(h, w, d_feats, d_img_index, d_input_ids, B, L, st));
     for (int t = 0; t < max_new; ++t) {
         // one new decoder row per pair: position t, input = token t-1 (start token for t = 0), self-attention over the cache
-        RUN(decoder_pass(h, w, d_tokens, max_new, B, L, 1, st, t, true));
-        HIPCHK(h, vqs::launch_argmax_append(w.logits, w.ldl, h->c.vocab, d_tokens, max_new, B, 1, st, t, w.flags), "argmax");   // + status bit 1 on a non-finite logit
+        VQS_RUN(decoder_pass(h, w, d_tokens, max_new, B, L, 1, st, t, true));
+        VQS_HIP(h, vqs::launch_argmax_append(w.logits, w.ldl, h->c.vocab, d_tokens, max_new, B, 1, st, t, w.flags), "argmax");   // + status bit 1 on a non-finite logit
     }
     return VQS_OK;
 }
@@ -1411,48 +1233,19 @@ int64_t vqs_workspace_offset(const vqs_handle* h, const char* name, int32_t B, i
 
 int vqs_profile_enable(vqs_handle* h, int32_t on) {
     if (!h) return VQS_ERR_INVALID;
-    h->prof = on != 0;
+    h->prof.on = on != 0;
     return VQS_OK;
 }
 
 int vqs_profile_read(vqs_handle* h, double* gemm_ms, double* gemm_flops, int32_t reset) {
-    if (!h) return VQS_ERR_INVALID;
-    double ms = 0.0;
-    std::map<std::string, std::array<double, 3>> by;      // label -> {launches, ms, flops}
-    for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-        HIPCHK(h, hipEventSynchronize(h->ev[i + 1]), "hipEventSynchronize");
-        float t = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]), "hipEventElapsedTime");
-        ms += t;
-        if (i / 2 < h->ev_what.size()) {
-            auto& a = by[h->ev_what[i / 2].first];
-            a[0] += 1.0; a[1] += t; a[2] += h->ev_what[i / 2].second;
-        }
-    }
-    h->prof_report.clear();
-    for (const auto& kv : by) {
-        char line[256];
-        snprintf(line, sizeof line, "%-20s launches %6.0f  ms %10.3f  TFLOP/s %8.1f\n", kv.first.c_str(), kv.second[0], kv.second[1],
-                 kv.second[1] > 0 ? kv.second[2] / kv.second[1] / 1e9 : 0.0);
-        h->prof_report += line;
-    }
-    if (gemm_ms) *gemm_ms = ms;
-    if (gemm_flops) *gemm_flops = h->prof_flops;
-    const int n = (int)(h->ev_used / 2);
-    if (reset) {
-        h->ev_used = 0;
-        h->ev_what.clear();
-        h->prof_flops = 0.0;
-        h->prof_bytes = 0.0;
-    }
-    return n;
+    return h ? vqs::profile_read(h, gemm_ms, gemm_flops, nullptr, reset != 0) : VQS_ERR_INVALID;
 }
 
-const char* vqs_profile_report(vqs_handle* h) { return h ? h->prof_report.c_str() : ""; }
+const char* vqs_profile_report(vqs_handle* h) { return h ? h->prof.report.c_str() : ""; }
 
 int vqs_profile_bytes(vqs_handle* h, double* gemm_bytes) {
     if (!h || !gemm_bytes) return VQS_ERR_INVALID;
-    *gemm_bytes = h->prof_bytes;
+    *gemm_bytes = h->prof.bytes;
     return VQS_OK;
 }
 
@@ -1509,14 +1302,12 @@ int vqs_debug_attention_f16(const void* q, const void* k, const void* v, void* o
     return vqs::launch_attention(a, (hipStream_t)stream) == hipSuccess ? VQS_OK : VQS_ERR_HIP;
 }
 
-static int debug_rc(hipError_t e) { return e == hipSuccess ? VQS_OK : e == hipErrorInvalidValue ? VQS_ERR_INVALID : VQS_ERR_HIP; }
-
 int vqs_debug_qwen_attention(const void* q, const void* k, const void* v, void* out, const int32_t* key_len, int32_t B, int32_t H, int32_t Hkv,
                              int32_t S, float scale, int32_t f16, void* stream) {
     if (!q || !k || !v || !out || !key_len) return VQS_ERR_INVALID;
     vqs::AttnParams a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, nullptr, key_len, B, H, S, scale};
     a.hd = 128; a.Hkv = Hkv; a.causal = 1; a.f16 = f16 ? 1 : 0;
-    return debug_rc(vqs::launch_attention(a, (hipStream_t)stream));
+    return vqs::abi_code(vqs::launch_attention(a, (hipStream_t)stream));
 }
 
 int vqs_debug_qwen_attention_suffix(const void* q, const void* k, const void* v, void* out, const int32_t* key_len, int32_t B, int32_t H,
@@ -1524,13 +1315,13 @@ int vqs_debug_qwen_attention_suffix(const void* q, const void* k, const void* v,
     if (!q || !k || !v || !out || !key_len) return VQS_ERR_INVALID;
     vqs::AttnSuffixParams a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, key_len, B, H, Hkv, S, Sq, q0, scale};
     a.f16 = f16 ? 1 : 0;
-    return debug_rc(vqs::launch_attention_suffix(a, (hipStream_t)stream));
+    return vqs::abi_code(vqs::launch_attention_suffix(a, (hipStream_t)stream));
 }
 
 int vqs_debug_qwen_kv_assemble(const void* pk, const void* pv, const void* sk, const void* sv, const int32_t* media_idx, void* dk, void* dv,
                                int32_t B, int32_t U, int32_t Hkv, int32_t Lp, int32_t Ls, void* stream) {
     if (!pk || !pv || !sk || !sv || !media_idx || !dk || !dv) return VQS_ERR_INVALID;
-    return debug_rc(vqs::launch_qwen_kv_assemble((const bf16_t*)pk, (const bf16_t*)pv, (const bf16_t*)sk, (const bf16_t*)sv, media_idx, (bf16_t*)dk,
+    return vqs::abi_code(vqs::launch_qwen_kv_assemble((const bf16_t*)pk, (const bf16_t*)pv, (const bf16_t*)sk, (const bf16_t*)sv, media_idx, (bf16_t*)dk,
                                                  (bf16_t*)dv, B, U, Hkv, Lp, Ls, (hipStream_t)stream));
 }
 
@@ -1546,7 +1337,7 @@ int vqs_debug_norm16(int32_t kind, float* x, const void* delta, const void* delt
                                   (const bf16_t*)delta2, store_x != 0, true);
     else
         return VQS_ERR_INVALID;
-    return e == hipSuccess ? VQS_OK : (e == hipErrorInvalidValue ? VQS_ERR_INVALID : VQS_ERR_HIP);
+    return vqs::abi_code(e);
 }
 
 int vqs_normalize_u8(const void* d_u8, void* d_out, int32_t N, int32_t H, int32_t W, const float* mean3, const float* std3,
@@ -1589,7 +1380,7 @@ int vqs_norm_deferred(int32_t kind, float* x, const void* delta, const void* del
                               (const bf16_t*)delta2, store_x != 0)
         : vqs::launch_layernorm(x, (const bf16_t*)delta, (const bf16_t*)w, (const bf16_t*)b, out, 0, M, D, eps, (hipStream_t)stream,
                                 (const bf16_t*)delta2, store_x != 0);
-    return e == hipSuccess ? VQS_OK : (e == hipErrorInvalidValue ? VQS_ERR_INVALID : VQS_ERR_HIP);
+    return vqs::abi_code(e);
 }
 
 int vqs_layernorm(float* x, const void* delta, const void* w, const void* b, void* out, int32_t out_f32, int32_t M, int32_t D,

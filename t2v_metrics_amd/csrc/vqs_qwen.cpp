@@ -7,7 +7,7 @@
 // both stacks; K dimensions are zero-padded to multiples of 64, gate|up rows interleaved in blocks of 32 for the gated
 // epilogue.  No device allocation, no stream synchronisation, no CPU fallback.
 #include "../../include/vqs_qwen.h"
-#include "vqs_kernels.h"
+#include "vqs_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -20,23 +20,21 @@
 #include <vector>
 
 using vqs::bf16_t;
+using vqs::align_up;
+using vqs::Carver;
+using vqs::fail;
+using vqs::GemmCall;
+using vqs::run_gemm;
+using vqs::tap2d;
 
 namespace {
 constexpr int HDP = 128;   // padded head width
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct WEnt {
-    const bf16_t* p;
-    int64_t numel;
-};
 }  // namespace
 
-struct vqs_qwen_handle {
+struct vqs_qwen_handle : vqs::HostBase {
+    vqs_qwen_handle() { numel_code = VQS_ERR_MISSING_WEIGHT; }      // see HostBase::numel_code: kept, not chosen
     vqs_qwen_config c;
-    std::string err;
-    std::unordered_map<std::string, WEnt> w;
-    bool bound = false;
     // tower heads narrower than 128 lanes whose q | k | v ranges are whole 128-column blocks (7B: 16 x 80): the qkv product keeps its
     // 3 x hidden columns (the GEMM scatters every head into the first v_hd lanes of a 128-lane slot, the other lanes are zeroed once
     // per call), attention writes its output compact and proj contracts over hidden -- 37.5 % fewer flops in both GEMMs at 80 lanes.
@@ -55,14 +53,6 @@ struct vqs_qwen_handle {
     const bf16_t* patch_w = nullptr;
     std::vector<const bf16_t*> v_qkv_w, v_qkv_b, v_proj_w, v_gu_w, v_gu_b, v_down_w;
     std::vector<const bf16_t*> t_qkv_w, t_qkv_b, t_o_w, t_gu_w, t_down_w;
-    // GEMM launch timing for bench roofline numbers (HIP events on the launch stream, as in vqs_api.cpp)
-    bool prof = false;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
-    double prof_flops = 0.0, prof_bytes = 0.0;
-    // stage taps (vqs_qwen_debug_tap): point name -> (caller buffer, capacity); a pass copies the named intermediate there
-    struct Tap { void* dst; size_t cap; };
-    std::unordered_map<std::string, Tap> taps;
     // 1 (default, round 5) = vqs_qwen_score / vqs_qwen_prefill re-evaluate every sample's LAST prompt position -- the one row that feeds the
     // head -- layer by layer with 16 significant bits (split-bf16 operands as stacked rows of the same GEMMs, fp32 partial sums, fp32
     // q and softmax over the layer's bf16 K / V) and take the logits from that row: the "precise tail" (tail_pass below; the analogue of the
@@ -93,61 +83,6 @@ struct vqs_qwen_handle {
 
 namespace {
 
-int qfail(vqs_qwen_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
-}
-
-#define QHIP(h, expr, what)                                                                                         \
-    do {                                                                                                            \
-        hipError_t _e = (expr);                                                                                     \
-        if (_e != hipSuccess) return qfail((h), VQS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(_e));     \
-    } while (0)
-#define QRUN(expr)                   \
-    do {                             \
-        int _r = (expr);             \
-        if (_r != VQS_OK) return _r; \
-    } while (0)
-
-// Copy an intermediate to a caller buffer registered with vqs_qwen_debug_tap (in-stream, device to device): the workspace buffers
-// are reused block after block, so this is how tests/test_gpu_qwen.py checks EVERY launch of a pass against the rounding-matched
-// oracle on the engine's own inputs.  One empty() test when nothing is registered.
-int qtap(vqs_qwen_handle* h, const char* stack, int layer, const char* what, const void* src, size_t bytes, hipStream_t st) {
-    if (h->taps.empty()) return VQS_OK;
-    const std::string name = layer >= 0 ? std::string(stack) + "." + std::to_string(layer) + "." + what : std::string(stack) + "." + what;
-    auto it = h->taps.find(name);
-    if (it == h->taps.end()) return VQS_OK;
-    if (it->second.cap < bytes) return qfail(h, VQS_ERR_WORKSPACE, "tap " + name + ": buffer too small (" + std::to_string(bytes) + " bytes needed)");
-    QHIP(h, hipMemcpyAsync(it->second.dst, src, bytes, hipMemcpyDeviceToDevice, st), "tap copy");
-    return VQS_OK;
-}
-// the same for a tensor whose rows sit at a pitch: the tap receives the dense [rows, width] tensor
-int qtap2d(vqs_qwen_handle* h, const char* stack, int layer, const char* what, const bf16_t* src, int width, int rows, int pitch, hipStream_t st) {
-    if (h->taps.empty()) return VQS_OK;
-    if (pitch == width) return qtap(h, stack, layer, what, src, (size_t)rows * width * sizeof(bf16_t), st);
-    const std::string name = layer >= 0 ? std::string(stack) + "." + std::to_string(layer) + "." + what : std::string(stack) + "." + what;
-    auto it = h->taps.find(name);
-    if (it == h->taps.end()) return VQS_OK;
-    const size_t bytes = (size_t)rows * width * sizeof(bf16_t);
-    if (it->second.cap < bytes) return qfail(h, VQS_ERR_WORKSPACE, "tap " + name + ": buffer too small (" + std::to_string(bytes) + " bytes needed)");
-    QHIP(h, hipMemcpy2DAsync(it->second.dst, (size_t)width * sizeof(bf16_t), src, (size_t)pitch * sizeof(bf16_t), (size_t)width * sizeof(bf16_t),
-                             (size_t)rows, hipMemcpyDeviceToDevice, st), "tap copy");
-    return VQS_OK;
-}
-#define QTAP(stack, layer, what, ptr, elems) QRUN(qtap(h, stack, layer, what, ptr, (size_t)(elems) * sizeof(*(ptr)), st))
-
-int get_w(vqs_qwen_handle* h, const std::string& name, int64_t numel, const bf16_t** out) {
-    auto it = h->w.find(name);
-    if (it == h->w.end()) return qfail(h, VQS_ERR_MISSING_WEIGHT, "missing weight " + name);
-    if (it->second.numel != numel)
-        return qfail(h, VQS_ERR_MISSING_WEIGHT, "weight " + name + " has " + std::to_string(it->second.numel) + " elements, expected " + std::to_string(numel));
-    *out = it->second.p;
-    return VQS_OK;
-}
-#define QW(var, name, numel)                                      \
-    const bf16_t* var = nullptr;                                  \
-    QRUN(get_w(h, (name), (int64_t)(numel), &var))
-
 // rows (or columns) of a head-major [n heads x hd] range laid into n x 128 lanes, -1 = zero
 std::vector<int> head_pad_map(int n, int hd) {
     std::vector<int> m((size_t)n * HDP);
@@ -165,62 +100,6 @@ std::vector<int> gate_up_map(int mlp, int mlp_p) {
     return m;
 }
 
-struct Carver {
-    char* base;
-    size_t off = 0;
-    template <typename T>
-    T* take(size_t n) {
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off = align_up(off + n * sizeof(T));
-        return p;
-    }
-};
-
-struct GCall {
-    const bf16_t* A;
-    const bf16_t* W;
-    void* C;
-    const bf16_t* bias = nullptr;
-    int M = 0, N = 0, K = 0, lda = 0, ldw = 0, ldc = 0, epi = 0;
-    int S = 0, H = 0, inner = 0, hd = 0, inner_kv = 0, Hkv = 0, gate_act = 0, hd_src = 0;
-    bf16_t* heads[3] = {nullptr, nullptr, nullptr};
-    int f16 = 0;                         // 3: the scaled fp16 family (A, W, result fp16; acc_scale / out_scale)
-    float acc_scale = 1.0f, out_scale = 1.0f;
-    const float *rope_cos = nullptr, *rope_sin = nullptr;     // f16 = 3, EPI_HEADS: rotary embedding in the epilogue (vqs_kernels.h)
-};
-
-int qgemm(vqs_qwen_handle* h, const GCall& g, hipStream_t st, const char* what) {
-    vqs::GemmParams p;
-    p.A = g.A; p.W = g.W; p.C = g.C; p.bias = g.bias; p.resid = nullptr;
-    p.M = g.M; p.N = g.N; p.K = g.K; p.lda = g.lda; p.ldw = g.ldw; p.ldc = g.ldc;
-    p.S = g.S > 0 ? g.S : 1; p.H = g.H; p.inner = g.inner > 0 ? g.inner : 1;
-    p.heads_out[0] = g.heads[0]; p.heads_out[1] = g.heads[1]; p.heads_out[2] = g.heads[2];
-    p.hd = g.hd; p.inner_kv = g.inner_kv; p.Hkv = g.Hkv; p.gate_act = g.gate_act; p.hd_src = g.hd_src;
-    p.f16 = g.f16; p.acc_scale = g.acc_scale; p.out_scale = g.out_scale;
-    p.rope_cos = g.rope_cos; p.rope_sin = g.rope_sin;
-    if (h->prof) {
-        while (h->ev.size() < h->ev_used + 2) {
-            hipEvent_t e;
-            QHIP(h, hipEventCreate(&e), "hipEventCreate");
-            h->ev.push_back(e);
-        }
-        QHIP(h, hipEventRecord(h->ev[h->ev_used], st), "hipEventRecord");
-    }
-    QHIP(h, vqs::launch_gemm(p, g.epi, 3, st), std::string("gemm ") + what);
-    if (h->prof) {
-        QHIP(h, hipEventRecord(h->ev[h->ev_used + 1], st), "hipEventRecord");
-        h->ev_used += 2;
-        h->prof_flops += 2.0 * (double)g.M * (double)g.N * (double)g.K;
-        const double out_n = (g.epi == vqs::EPI_GATED) ? 0.5 * (double)g.N : (double)g.N;
-        h->prof_bytes += 2.0 * ((double)g.M + (double)g.N) * (double)g.K + ((g.epi == vqs::EPI_F32) ? 4.0 : 2.0) * (double)g.M * out_n;
-    }
-    return VQS_OK;
-}
-
-struct PackPlan {
-    size_t total = 0;
-};
-
 // One pass that either sizes (base == nullptr) or performs the packing.
 int pack(vqs_qwen_handle* h, char* base, size_t* total, hipStream_t st) {
     const vqs_qwen_config& c = h->c;
@@ -228,23 +107,23 @@ int pack(vqs_qwen_handle* h, char* base, size_t* total, hipStream_t st) {
     auto up_map = [&](const std::vector<int>& m, const int** dptr) -> int {
         int* d = cv.take<int>(m.size());
         if (base) {
-            QHIP(h, hipMemcpyAsync(d, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice, st), "upload packing map");
+            VQS_HIP(h, hipMemcpyAsync(d, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice, st), "upload packing map");
             *dptr = d;
         }
         return VQS_OK;
     };
-    QRUN(up_map(h->m_vheads, &h->d_vheads));
-    QRUN(up_map(h->m_theads, &h->d_theads));
-    QRUN(up_map(h->m_tkv, &h->d_tkv));
-    QRUN(up_map(h->m_vgate, &h->d_vgate));
-    QRUN(up_map(h->m_tgate, &h->d_tgate));
+    VQS_RUN(up_map(h->m_vheads, &h->d_vheads));
+    VQS_RUN(up_map(h->m_theads, &h->d_theads));
+    VQS_RUN(up_map(h->m_tkv, &h->d_tkv));
+    VQS_RUN(up_map(h->m_vgate, &h->d_vgate));
+    VQS_RUN(up_map(h->m_tgate, &h->d_tgate));
 
     const int VH = c.v_hidden, VHD = h->v_hd, VNH = c.v_heads, VPK = VNH * HDP;
     {   // patch embed: [hidden, patch_dim] -> K padded to 64
         bf16_t* d = cv.take<bf16_t>((size_t)VH * h->v_kpatch);
         if (base) {
-            QW(w, "model.visual.patch_embed.proj.weight", (int64_t)VH * c.v_patch_dim);
-            QHIP(h, vqs::launch_gather_rows_bf16(w, nullptr, nullptr, d, VH, c.v_patch_dim, c.v_patch_dim, h->v_kpatch, st), "pack patch embed");
+            VQS_W(w, "model.visual.patch_embed.proj.weight", (int64_t)VH * c.v_patch_dim);
+            VQS_HIP(h, vqs::launch_gather_rows_bf16(w, nullptr, nullptr, d, VH, c.v_patch_dim, c.v_patch_dim, h->v_kpatch, st), "pack patch embed");
             h->patch_w = d;
         }
     }
@@ -273,32 +152,32 @@ int pack(vqs_qwen_handle* h, char* base, size_t* total, hipStream_t st) {
             qkv_h = cv.take<bf16_t>(n_qkv); proj_h = cv.take<bf16_t>(n_proj); gu_h = cv.take<bf16_t>(n_gu); down_h = cv.take<bf16_t>(n_down);
         }
         if (!base) continue;
-        QW(wqkv, p + "attn.qkv.weight", (int64_t)3 * VH * VH);
-        QW(bqkv, p + "attn.qkv.bias", 3 * VH);
-        QW(wproj, p + "attn.proj.weight", (int64_t)VH * VH);
-        QW(wg, p + "mlp.gate_proj.weight", (int64_t)c.v_mlp * VH);
-        QW(bg, p + "mlp.gate_proj.bias", c.v_mlp);
-        QW(wu, p + "mlp.up_proj.weight", (int64_t)c.v_mlp * VH);
-        QW(bu, p + "mlp.up_proj.bias", c.v_mlp);
-        QW(wd, p + "mlp.down_proj.weight", (int64_t)VH * c.v_mlp);
+        VQS_W(wqkv, p + "attn.qkv.weight", (int64_t)3 * VH * VH);
+        VQS_W(bqkv, p + "attn.qkv.bias", 3 * VH);
+        VQS_W(wproj, p + "attn.proj.weight", (int64_t)VH * VH);
+        VQS_W(wg, p + "mlp.gate_proj.weight", (int64_t)c.v_mlp * VH);
+        VQS_W(bg, p + "mlp.gate_proj.bias", c.v_mlp);
+        VQS_W(wu, p + "mlp.up_proj.weight", (int64_t)c.v_mlp * VH);
+        VQS_W(bu, p + "mlp.up_proj.bias", c.v_mlp);
+        VQS_W(wd, p + "mlp.down_proj.weight", (int64_t)VH * c.v_mlp);
         for (int which = 0; which < 3 && !cp; ++which) {   // q | k | v row ranges, every head padded to 128 rows
-            QHIP(h, vqs::launch_gather_rows_bf16(wqkv + (size_t)which * VH * VH, nullptr, h->d_vheads, qkv + (size_t)which * VPK * VH,
+            VQS_HIP(h, vqs::launch_gather_rows_bf16(wqkv + (size_t)which * VH * VH, nullptr, h->d_vheads, qkv + (size_t)which * VPK * VH,
                                                   VPK, VH, VH, VH, st), "pack vision qkv");
-            QHIP(h, vqs::launch_gather_rows_bf16(bqkv + (size_t)which * VH, nullptr, h->d_vheads, qkvb + (size_t)which * VPK, VPK, 1, 1, 1, st),
+            VQS_HIP(h, vqs::launch_gather_rows_bf16(bqkv + (size_t)which * VH, nullptr, h->d_vheads, qkvb + (size_t)which * VPK, VPK, 1, 1, 1, st),
                  "pack vision qkv bias");
         }
-        if (!cp) QHIP(h, vqs::launch_gather_cols_bf16(wproj, h->d_vheads, proj, VH, VH, VPK, st), "pack vision proj");
+        if (!cp) VQS_HIP(h, vqs::launch_gather_cols_bf16(wproj, h->d_vheads, proj, VH, VH, VPK, st), "pack vision proj");
         if (cp) { qkv = const_cast<bf16_t*>(wqkv); qkvb = const_cast<bf16_t*>(bqkv); proj = const_cast<bf16_t*>(wproj); }
-        QHIP(h, vqs::launch_gather_rows_bf16(wg, wu, h->d_vgate, gu, 2 * h->v_mlp_p, VH, VH, VH, st), "pack vision gate|up");
-        QHIP(h, vqs::launch_gather_rows_bf16(bg, bu, h->d_vgate, gub, 2 * h->v_mlp_p, 1, 1, 1, st), "pack vision gate|up bias");
-        QHIP(h, vqs::launch_gather_rows_bf16(wd, nullptr, nullptr, down, VH, c.v_mlp, c.v_mlp, h->v_ffld, st), "pack vision down");
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(wg, wu, h->d_vgate, gu, 2 * h->v_mlp_p, VH, VH, VH, st), "pack vision gate|up");
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(bg, bu, h->d_vgate, gub, 2 * h->v_mlp_p, 1, 1, 1, st), "pack vision gate|up bias");
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(wd, nullptr, nullptr, down, VH, c.v_mlp, c.v_mlp, h->v_ffld, st), "pack vision down");
         (void)VHD;
         h->v_qkv_w[i] = qkv; h->v_qkv_b[i] = qkvb; h->v_proj_w[i] = proj; h->v_gu_w[i] = gu; h->v_gu_b[i] = gub; h->v_down_w[i] = down;
         if (h->fp16_req) {
-            QHIP(h, vqs::launch_cast16(qkv, qkv_h, n_qkv, true, st), "fp16 vision qkv");
-            QHIP(h, vqs::launch_cast16(proj, proj_h, n_proj, true, st), "fp16 vision proj");
-            QHIP(h, vqs::launch_cast16(gu, gu_h, n_gu, true, st), "fp16 vision gate|up");
-            QHIP(h, vqs::launch_cast16(down, down_h, n_down, true, st), "fp16 vision down");
+            VQS_HIP(h, vqs::launch_cast16(qkv, qkv_h, n_qkv, true, st), "fp16 vision qkv");
+            VQS_HIP(h, vqs::launch_cast16(proj, proj_h, n_proj, true, st), "fp16 vision proj");
+            VQS_HIP(h, vqs::launch_cast16(gu, gu_h, n_gu, true, st), "fp16 vision gate|up");
+            VQS_HIP(h, vqs::launch_cast16(down, down_h, n_down, true, st), "fp16 vision down");
             h->v_qkv_h[i] = qkv_h; h->v_proj_h[i] = proj_h; h->v_gu_h[i] = gu_h; h->v_down_h[i] = down_h;
         }
     }
@@ -307,10 +186,10 @@ int pack(vqs_qwen_handle* h, char* base, size_t* total, hipStream_t st) {
         bf16_t *m0 = nullptr, *m2 = nullptr;
         if (h->fp16_req) { m0 = cv.take<bf16_t>(n0); m2 = cv.take<bf16_t>(n2); }
         if (base && h->fp16_req) {
-            QW(m0w, "model.visual.merger.mlp.0.weight", (int64_t)n0);
-            QW(m2w, "model.visual.merger.mlp.2.weight", (int64_t)n2);
-            QHIP(h, vqs::launch_cast16(m0w, m0, n0, true, st), "fp16 merger mlp.0");
-            QHIP(h, vqs::launch_cast16(m2w, m2, n2, true, st), "fp16 merger mlp.2");
+            VQS_W(m0w, "model.visual.merger.mlp.0.weight", (int64_t)n0);
+            VQS_W(m2w, "model.visual.merger.mlp.2.weight", (int64_t)n2);
+            VQS_HIP(h, vqs::launch_cast16(m0w, m0, n0, true, st), "fp16 merger mlp.0");
+            VQS_HIP(h, vqs::launch_cast16(m2w, m2, n2, true, st), "fp16 merger mlp.2");
             h->m0_h = m0; h->m2_h = m2;
         }
     }
@@ -329,31 +208,31 @@ int pack(vqs_qwen_handle* h, char* base, size_t* total, hipStream_t st) {
         }
         if (!base) continue;
         const int64_t qn = (int64_t)c.t_heads * thd, kn = (int64_t)c.t_kv_heads * thd;
-        QW(wq, p + "self_attn.q_proj.weight", qn * TH);
-        QW(bq, p + "self_attn.q_proj.bias", qn);
-        QW(wk, p + "self_attn.k_proj.weight", kn * TH);
-        QW(bk, p + "self_attn.k_proj.bias", kn);
-        QW(wv, p + "self_attn.v_proj.weight", kn * TH);
-        QW(bv, p + "self_attn.v_proj.bias", kn);
-        QW(wo, p + "self_attn.o_proj.weight", (int64_t)TH * qn);
-        QW(wg, p + "mlp.gate_proj.weight", (int64_t)c.t_mlp * TH);
-        QW(wu, p + "mlp.up_proj.weight", (int64_t)c.t_mlp * TH);
-        QW(wd, p + "mlp.down_proj.weight", (int64_t)TH * c.t_mlp);
-        QHIP(h, vqs::launch_gather_rows_bf16(wq, nullptr, h->d_theads, qkv, IQ, TH, TH, TH, st), "pack q");
-        QHIP(h, vqs::launch_gather_rows_bf16(wk, nullptr, h->d_tkv, qkv + (size_t)IQ * TH, IKV, TH, TH, TH, st), "pack k");
-        QHIP(h, vqs::launch_gather_rows_bf16(wv, nullptr, h->d_tkv, qkv + (size_t)(IQ + IKV) * TH, IKV, TH, TH, TH, st), "pack v");
-        QHIP(h, vqs::launch_gather_rows_bf16(bq, nullptr, h->d_theads, qkvb, IQ, 1, 1, 1, st), "pack q bias");
-        QHIP(h, vqs::launch_gather_rows_bf16(bk, nullptr, h->d_tkv, qkvb + IQ, IKV, 1, 1, 1, st), "pack k bias");
-        QHIP(h, vqs::launch_gather_rows_bf16(bv, nullptr, h->d_tkv, qkvb + IQ + IKV, IKV, 1, 1, 1, st), "pack v bias");
-        QHIP(h, vqs::launch_gather_cols_bf16(wo, h->d_theads, ow, TH, (int)qn, IQ, st), "pack o");
-        QHIP(h, vqs::launch_gather_rows_bf16(wg, wu, h->d_tgate, gu, 2 * h->t_mlp_p, TH, TH, h->t_xld, st), "pack gate|up");
-        QHIP(h, vqs::launch_gather_rows_bf16(wd, nullptr, nullptr, down, TH, c.t_mlp, c.t_mlp, h->t_ffld, st), "pack down");
+        VQS_W(wq, p + "self_attn.q_proj.weight", qn * TH);
+        VQS_W(bq, p + "self_attn.q_proj.bias", qn);
+        VQS_W(wk, p + "self_attn.k_proj.weight", kn * TH);
+        VQS_W(bk, p + "self_attn.k_proj.bias", kn);
+        VQS_W(wv, p + "self_attn.v_proj.weight", kn * TH);
+        VQS_W(bv, p + "self_attn.v_proj.bias", kn);
+        VQS_W(wo, p + "self_attn.o_proj.weight", (int64_t)TH * qn);
+        VQS_W(wg, p + "mlp.gate_proj.weight", (int64_t)c.t_mlp * TH);
+        VQS_W(wu, p + "mlp.up_proj.weight", (int64_t)c.t_mlp * TH);
+        VQS_W(wd, p + "mlp.down_proj.weight", (int64_t)TH * c.t_mlp);
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(wq, nullptr, h->d_theads, qkv, IQ, TH, TH, TH, st), "pack q");
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(wk, nullptr, h->d_tkv, qkv + (size_t)IQ * TH, IKV, TH, TH, TH, st), "pack k");
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(wv, nullptr, h->d_tkv, qkv + (size_t)(IQ + IKV) * TH, IKV, TH, TH, TH, st), "pack v");
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(bq, nullptr, h->d_theads, qkvb, IQ, 1, 1, 1, st), "pack q bias");
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(bk, nullptr, h->d_tkv, qkvb + IQ, IKV, 1, 1, 1, st), "pack k bias");
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(bv, nullptr, h->d_tkv, qkvb + IQ + IKV, IKV, 1, 1, 1, st), "pack v bias");
+        VQS_HIP(h, vqs::launch_gather_cols_bf16(wo, h->d_theads, ow, TH, (int)qn, IQ, st), "pack o");
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(wg, wu, h->d_tgate, gu, 2 * h->t_mlp_p, TH, TH, h->t_xld, st), "pack gate|up");
+        VQS_HIP(h, vqs::launch_gather_rows_bf16(wd, nullptr, nullptr, down, TH, c.t_mlp, c.t_mlp, h->t_ffld, st), "pack down");
         h->t_qkv_w[i] = qkv; h->t_qkv_b[i] = qkvb; h->t_o_w[i] = ow; h->t_gu_w[i] = gu; h->t_down_w[i] = down;
         if (h->fp16_req) {
-            QHIP(h, vqs::launch_cast16(qkv, qkv_h, n_qkv, true, st), "fp16 qkv");
-            QHIP(h, vqs::launch_cast16(ow, o_h, n_o, true, st), "fp16 o");
-            QHIP(h, vqs::launch_cast16(gu, gu_h, n_gu, true, st), "fp16 gate|up");
-            QHIP(h, vqs::launch_cast16(down, down_h, n_down, true, st), "fp16 down");
+            VQS_HIP(h, vqs::launch_cast16(qkv, qkv_h, n_qkv, true, st), "fp16 qkv");
+            VQS_HIP(h, vqs::launch_cast16(ow, o_h, n_o, true, st), "fp16 o");
+            VQS_HIP(h, vqs::launch_cast16(gu, gu_h, n_gu, true, st), "fp16 gate|up");
+            VQS_HIP(h, vqs::launch_cast16(down, down_h, n_down, true, st), "fp16 down");
             h->t_qkv_h[i] = qkv_h; h->t_o_h[i] = o_h; h->t_gu_h[i] = gu_h; h->t_down_h[i] = down_h;
         }
     }
@@ -367,7 +246,7 @@ int pack(vqs_qwen_handle* h, char* base, size_t* total, hipStream_t st) {
         float* sl = cv.take<float>(h->n_slots);
         if (base) { h->d_rb = rb; h->d_ucol = uc; h->d_slots = sl; }
     }
-    *total = align_up(cv.off);
+    *total = cv.total();
     return VQS_OK;
 }
 
@@ -396,69 +275,69 @@ int compute_ranges(vqs_qwen_handle* h, hipStream_t st) {
     const bool cp = h->v_compact;
     const int VAK = cp ? VH : VPK, VQN = cp ? 3 * VH : 3 * VPK;
     float* sl = h->d_slots;
-    QHIP(h, hipMemsetAsync(sl, 0, h->n_slots * sizeof(float), st), "clear range slots");
+    VQS_HIP(h, hipMemsetAsync(sl, 0, h->n_slots * sizeof(float), st), "clear range slots");
     // slot layout: block / layer l at 8 l: [x0, qkv (before the rotary embedding), dattn, x1, gate|up rows (unused), act, dmlp, -]; then the
     // merger's [x, mid, out] and the largest |weight|
     auto layer_chain = [&](float* s8, const bf16_t* g1, const bf16_t* g2, int D, const bf16_t* wqkv, int nq, const bf16_t* bqkv, const bf16_t* wo,
                            int ko, const bf16_t* bo, const bf16_t* wgu, long long ld_gu, int mlp_p, const bf16_t* bgu, const bf16_t* wd, int ffld,
                            const bf16_t* bd) -> int {
         const float R = std::sqrt((float)D);
-        QHIP(h, vqs::launch_absmax_bf16(g1, (size_t)D, R, s8 + 0, st), "range x0");
-        QHIP(h, vqs::launch_rowbound(wqkv, D, nq, D, 0, g1, D, R, nullptr, nullptr, bqkv, nullptr, s8 + 1, st), "range qkv");
-        QHIP(h, vqs::launch_rowbound(wo, ko, D, ko, 1, nullptr, 0, 0.0f, nullptr, s8 + 1, bo, nullptr, s8 + 2, st), "range attention output");
-        QHIP(h, vqs::launch_absmax_bf16(g2, (size_t)D, R, s8 + 3, st), "range x1");
-        QHIP(h, vqs::launch_rowbound(wgu, ld_gu, 2 * mlp_p, D, 0, g2, D, R, nullptr, nullptr, bgu, h->d_rb, s8 + 4, st), "range gate|up");
-        QHIP(h, vqs::launch_gate_pair_bound(h->d_rb, mlp_p, ffld, h->d_ucol, s8 + 5, st), "range gated product");
-        QHIP(h, vqs::launch_rowbound(wd, ffld, D, ffld, 1, nullptr, 0, 0.0f, h->d_ucol, nullptr, bd, nullptr, s8 + 6, st), "range FFN output");
+        VQS_HIP(h, vqs::launch_absmax_bf16(g1, (size_t)D, R, s8 + 0, st), "range x0");
+        VQS_HIP(h, vqs::launch_rowbound(wqkv, D, nq, D, 0, g1, D, R, nullptr, nullptr, bqkv, nullptr, s8 + 1, st), "range qkv");
+        VQS_HIP(h, vqs::launch_rowbound(wo, ko, D, ko, 1, nullptr, 0, 0.0f, nullptr, s8 + 1, bo, nullptr, s8 + 2, st), "range attention output");
+        VQS_HIP(h, vqs::launch_absmax_bf16(g2, (size_t)D, R, s8 + 3, st), "range x1");
+        VQS_HIP(h, vqs::launch_rowbound(wgu, ld_gu, 2 * mlp_p, D, 0, g2, D, R, nullptr, nullptr, bgu, h->d_rb, s8 + 4, st), "range gate|up");
+        VQS_HIP(h, vqs::launch_gate_pair_bound(h->d_rb, mlp_p, ffld, h->d_ucol, s8 + 5, st), "range gated product");
+        VQS_HIP(h, vqs::launch_rowbound(wd, ffld, D, ffld, 1, nullptr, 0, 0.0f, h->d_ucol, nullptr, bd, nullptr, s8 + 6, st), "range FFN output");
         return VQS_OK;
     };
     float* wmax = sl + (size_t)8 * (c.v_depth + c.t_layers) + 3;
     auto wrange = [&](const bf16_t* w, size_t n) -> int {
-        QHIP(h, vqs::launch_absmax_bf16(w, n, 1.0f, wmax, st), "weight range");
+        VQS_HIP(h, vqs::launch_absmax_bf16(w, n, 1.0f, wmax, st), "weight range");
         return VQS_OK;
     };
     for (int i = 0; i < c.v_depth; ++i) {
         const std::string p = "model.visual.blocks." + std::to_string(i) + ".";
-        QW(n1, p + "norm1.weight", VH);
-        QW(n2, p + "norm2.weight", VH);
-        QW(pb, p + "attn.proj.bias", VH);
-        QW(db, p + "mlp.down_proj.bias", VH);
-        QRUN(layer_chain(sl + (size_t)8 * i, n1, n2, VH, h->v_qkv_w[i], VQN, h->v_qkv_b[i], h->v_proj_w[i], VAK, pb, h->v_gu_w[i], VH, h->v_mlp_p,
+        VQS_W(n1, p + "norm1.weight", VH);
+        VQS_W(n2, p + "norm2.weight", VH);
+        VQS_W(pb, p + "attn.proj.bias", VH);
+        VQS_W(db, p + "mlp.down_proj.bias", VH);
+        VQS_RUN(layer_chain(sl + (size_t)8 * i, n1, n2, VH, h->v_qkv_w[i], VQN, h->v_qkv_b[i], h->v_proj_w[i], VAK, pb, h->v_gu_w[i], VH, h->v_mlp_p,
                          h->v_gu_b[i], h->v_down_w[i], h->v_ffld, db));
-        QRUN(wrange(h->v_qkv_w[i], (size_t)VQN * VH));
-        QRUN(wrange(h->v_proj_w[i], (size_t)VH * VAK));
-        QRUN(wrange(h->v_gu_w[i], (size_t)2 * h->v_mlp_p * VH));
-        QRUN(wrange(h->v_down_w[i], (size_t)VH * h->v_ffld));
+        VQS_RUN(wrange(h->v_qkv_w[i], (size_t)VQN * VH));
+        VQS_RUN(wrange(h->v_proj_w[i], (size_t)VH * VAK));
+        VQS_RUN(wrange(h->v_gu_w[i], (size_t)2 * h->v_mlp_p * VH));
+        VQS_RUN(wrange(h->v_down_w[i], (size_t)VH * h->v_ffld));
     }
     {   // merger: RMSNorm over VH, merge_unit rows concatenated (||x^cat||_2 <= sqrt(merge_unit VH)), Linear-GELU-Linear
         float* sm = sl + (size_t)8 * (c.v_depth + c.t_layers);
-        QW(lnq, "model.visual.merger.ln_q.weight", VH);
-        QW(m0w, "model.visual.merger.mlp.0.weight", (int64_t)h->merge_hidden * h->merge_hidden);
-        QW(m0b, "model.visual.merger.mlp.0.bias", h->merge_hidden);
-        QW(m2w, "model.visual.merger.mlp.2.weight", (int64_t)c.v_out_hidden * h->merge_hidden);
-        QW(m2b, "model.visual.merger.mlp.2.bias", c.v_out_hidden);
-        QHIP(h, vqs::launch_absmax_bf16(lnq, (size_t)VH, std::sqrt((float)VH), sm + 0, st), "range merger norm");
-        QHIP(h, vqs::launch_rowbound(m0w, h->merge_hidden, h->merge_hidden, h->merge_hidden, 0, lnq, VH, std::sqrt((float)h->merge_hidden), nullptr, nullptr,
+        VQS_W(lnq, "model.visual.merger.ln_q.weight", VH);
+        VQS_W(m0w, "model.visual.merger.mlp.0.weight", (int64_t)h->merge_hidden * h->merge_hidden);
+        VQS_W(m0b, "model.visual.merger.mlp.0.bias", h->merge_hidden);
+        VQS_W(m2w, "model.visual.merger.mlp.2.weight", (int64_t)c.v_out_hidden * h->merge_hidden);
+        VQS_W(m2b, "model.visual.merger.mlp.2.bias", c.v_out_hidden);
+        VQS_HIP(h, vqs::launch_absmax_bf16(lnq, (size_t)VH, std::sqrt((float)VH), sm + 0, st), "range merger norm");
+        VQS_HIP(h, vqs::launch_rowbound(m0w, h->merge_hidden, h->merge_hidden, h->merge_hidden, 0, lnq, VH, std::sqrt((float)h->merge_hidden), nullptr, nullptr,
                                      m0b, h->d_ucol, sm + 1, st), "range merger mlp.0");
-        QHIP(h, vqs::launch_rowbound(m2w, h->merge_hidden, c.v_out_hidden, h->merge_hidden, 1, nullptr, 0, 0.0f, h->d_ucol, nullptr, m2b, nullptr, sm + 2,
+        VQS_HIP(h, vqs::launch_rowbound(m2w, h->merge_hidden, c.v_out_hidden, h->merge_hidden, 1, nullptr, 0, 0.0f, h->d_ucol, nullptr, m2b, nullptr, sm + 2,
                                      st), "range merger mlp.2");
-        QRUN(wrange(m0w, (size_t)h->merge_hidden * h->merge_hidden));
-        QRUN(wrange(m2w, (size_t)c.v_out_hidden * h->merge_hidden));
+        VQS_RUN(wrange(m0w, (size_t)h->merge_hidden * h->merge_hidden));
+        VQS_RUN(wrange(m2w, (size_t)c.v_out_hidden * h->merge_hidden));
     }
     for (int i = 0; i < c.t_layers; ++i) {
         const std::string p = "model.language_model.layers." + std::to_string(i) + ".";
-        QW(ln1, p + "input_layernorm.weight", TH);
-        QW(ln2, p + "post_attention_layernorm.weight", TH);
-        QRUN(layer_chain(sl + (size_t)8 * (c.v_depth + i), ln1, ln2, TH, h->t_qkv_w[i], QN, h->t_qkv_b[i], h->t_o_w[i], IQ, nullptr, h->t_gu_w[i],
+        VQS_W(ln1, p + "input_layernorm.weight", TH);
+        VQS_W(ln2, p + "post_attention_layernorm.weight", TH);
+        VQS_RUN(layer_chain(sl + (size_t)8 * (c.v_depth + i), ln1, ln2, TH, h->t_qkv_w[i], QN, h->t_qkv_b[i], h->t_o_w[i], IQ, nullptr, h->t_gu_w[i],
                          h->t_xld, h->t_mlp_p, nullptr, h->t_down_w[i], h->t_ffld, nullptr));
-        QRUN(wrange(h->t_qkv_w[i], (size_t)QN * TH));
-        QRUN(wrange(h->t_o_w[i], (size_t)TH * IQ));
-        QRUN(wrange(h->t_gu_w[i], (size_t)2 * h->t_mlp_p * h->t_xld));
-        QRUN(wrange(h->t_down_w[i], (size_t)TH * h->t_ffld));
+        VQS_RUN(wrange(h->t_qkv_w[i], (size_t)QN * TH));
+        VQS_RUN(wrange(h->t_o_w[i], (size_t)TH * IQ));
+        VQS_RUN(wrange(h->t_gu_w[i], (size_t)2 * h->t_mlp_p * h->t_xld));
+        VQS_RUN(wrange(h->t_down_w[i], (size_t)TH * h->t_ffld));
     }
     std::vector<float> host(h->n_slots);
-    QHIP(h, hipMemcpyAsync(host.data(), sl, h->n_slots * sizeof(float), hipMemcpyDeviceToHost, st), "read range slots");
-    QHIP(h, hipStreamSynchronize(st), "range proof synchronise");
+    VQS_HIP(h, hipMemcpyAsync(host.data(), sl, h->n_slots * sizeof(float), hipMemcpyDeviceToHost, st), "read range slots");
+    VQS_HIP(h, hipStreamSynchronize(st), "range proof synchronise");
     bool ok = true;
     auto layer_sites = [&](vqs_qwen_handle::LayerSites& L, const float* s8) {
         ok &= site_from_bound(L.x0, s8[0]);
@@ -516,7 +395,7 @@ VisWs carve_vision(const vqs_qwen_handle* h, char* base, int N, int Np) {
     w.dc = cv.take<bf16_t>(n * c.v_hidden);
     w.mid = cv.take<bf16_t>(np / c.v_merge_unit * h->merge_hidden);
     w.merged_w = cv.take<bf16_t>(np / c.v_merge_unit * c.v_out_hidden);
-    w.total = align_up(cv.off);
+    w.total = cv.total();
     return w;
 }
 
@@ -578,7 +457,7 @@ TxtWs carve_text(const vqs_qwen_handle* h, char* base, int B, int L) {
         w.t_part_bytes = 2 * Bc * widest * sizeof(float);
         w.t_part = cv.take<float>(2 * Bc * widest);
     }
-    w.total = align_up(cv.off);
+    w.total = cv.total();
     return w;
 }
 
@@ -633,66 +512,49 @@ int vqs_qwen_create(const vqs_qwen_config* cfg, vqs_qwen_handle** out) {
     return VQS_OK;
 }
 
-void vqs_qwen_destroy(vqs_qwen_handle* h) {
-    if (!h) return;
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    delete h;
-}
+void vqs_qwen_destroy(vqs_qwen_handle* h) { delete h; }      // ~GemmProfile destroys the profile's events
 
 int vqs_qwen_profile_enable(vqs_qwen_handle* h, int32_t on) {
     if (!h) return VQS_ERR_INVALID;
-    h->prof = on != 0;
+    h->prof.on = on != 0;
     return VQS_OK;
 }
 
 int vqs_qwen_profile_read(vqs_qwen_handle* h, double* gemm_ms, double* gemm_flops, double* gemm_bytes, int32_t reset) {
-    if (!h) return VQS_ERR_INVALID;
-    double ms = 0.0;
-    for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-        QHIP(h, hipEventSynchronize(h->ev[i + 1]), "hipEventSynchronize");
-        float t = 0.f;
-        QHIP(h, hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]), "hipEventElapsedTime");
-        ms += t;
-    }
-    if (gemm_ms) *gemm_ms = ms;
-    if (gemm_flops) *gemm_flops = h->prof_flops;
-    if (gemm_bytes) *gemm_bytes = h->prof_bytes;
-    const int n = (int)(h->ev_used / 2);
-    if (reset) { h->ev_used = 0; h->prof_flops = 0.0; h->prof_bytes = 0.0; }
-    return n;
+    return h ? vqs::profile_read(h, gemm_ms, gemm_flops, gemm_bytes, reset != 0) : VQS_ERR_INVALID;
 }
 
 int vqs_qwen_debug_option(vqs_qwen_handle* h, const char* name, int64_t value) {
     if (!h || !name) return VQS_ERR_INVALID;
     if (std::string(name) == "x_pitch") {        // before vqs_qwen_bind_weights: the packed gate|up rows carry the pitch
-        if (h->bound) return qfail(h, VQS_ERR_STATE, "x_pitch must be set before the weights are bound");
+        if (h->bound) return fail(h, VQS_ERR_STATE, "x_pitch must be set before the weights are bound");
         if (value < h->c.t_hidden || (value % 64) != 0 || value > 8 * (int64_t)h->c.t_hidden + 4096)
-            return qfail(h, VQS_ERR_INVALID, "x_pitch: a multiple of 64 elements, >= hidden");
+            return fail(h, VQS_ERR_INVALID, "x_pitch: a multiple of 64 elements, >= hidden");
         h->t_xld = (int)value;
         return VQS_OK;
     }
     if (std::string(name) == "fp16") {           // see include/vqs_qwen.h: 1 needs an eligible model and must be asked for BEFORE the weights are bound
-        if (value != 0 && value != 1) return qfail(h, VQS_ERR_INVALID, "fp16: 0 or 1");
-        if (value == 1 && !h->fp16_eligible) return qfail(h, VQS_ERR_INVALID, "fp16: this configuration has contractions narrower than 128 or rotary halves that are not multiples of 8");
+        if (value != 0 && value != 1) return fail(h, VQS_ERR_INVALID, "fp16: 0 or 1");
+        if (value == 1 && !h->fp16_eligible) return fail(h, VQS_ERR_INVALID, "fp16: this configuration has contractions narrower than 128 or rotary halves that are not multiples of 8");
         if (!h->bound) { h->fp16_req = (int)value; return VQS_OK; }
         if (value == 0) { h->fp16_active = 0; return VQS_OK; }              // the bf16 forms are always there
-        if (!h->fp16_req) return qfail(h, VQS_ERR_STATE, "fp16: the weights were bound without fp16 copies; set the option before vqs_qwen_bind_weights");
-        if (h->t_sc.empty()) return qfail(h, VQS_ERR_STATE, "fp16: the range proof did not complete at bind time");
-        if (!(h->w_absmax < 65504.0f)) return qfail(h, VQS_ERR_STATE, "fp16: a weight does not fit IEEE fp16");
+        if (!h->fp16_req) return fail(h, VQS_ERR_STATE, "fp16: the weights were bound without fp16 copies; set the option before vqs_qwen_bind_weights");
+        if (h->t_sc.empty()) return fail(h, VQS_ERR_STATE, "fp16: the range proof did not complete at bind time");
+        if (!(h->w_absmax < 65504.0f)) return fail(h, VQS_ERR_STATE, "fp16: a weight does not fit IEEE fp16");
         h->fp16_active = 1;
         return VQS_OK;
     }
     if (std::string(name) == "rope_fused") {     // see vqs_qwen_handle::rope_fused
-        if (value != 0 && value != 1) return qfail(h, VQS_ERR_INVALID, "rope_fused: 0 or 1");
+        if (value != 0 && value != 1) return fail(h, VQS_ERR_INVALID, "rope_fused: 0 or 1");
         h->rope_fused = (int)value;
         return VQS_OK;
     }
     if (std::string(name) == "tail_precise") {   // see vqs_qwen_handle::tail_precise
-        if (value != 0 && value != 1) return qfail(h, VQS_ERR_INVALID, "tail_precise: 0 or 1");
+        if (value != 0 && value != 1) return fail(h, VQS_ERR_INVALID, "tail_precise: 0 or 1");
         h->tail_precise = (int)value;
         return VQS_OK;
     }
-    return qfail(h, VQS_ERR_INVALID, std::string("unknown option ") + name);
+    return fail(h, VQS_ERR_INVALID, std::string("unknown option ") + name);
 }
 
 int vqs_qwen_get_option(const vqs_qwen_handle* h, const char* name, int64_t* value) {
@@ -727,9 +589,7 @@ int vqs_qwen_range_report(const vqs_qwen_handle* h, float* bounds, float* sigmas
 
 int vqs_qwen_debug_tap(vqs_qwen_handle* h, const char* name, void* d_dst, size_t bytes) {
     if (!h) return VQS_ERR_INVALID;
-    if (!name) { h->taps.clear(); return VQS_OK; }
-    if (!d_dst || bytes == 0) { h->taps.erase(name); return VQS_OK; }
-    h->taps[name] = vqs_qwen_handle::Tap{d_dst, bytes};
+    h->taps.set(name, d_dst, bytes);
     return VQS_OK;
 }
 
@@ -744,41 +604,38 @@ size_t vqs_qwen_packed_bytes(const vqs_qwen_handle* h) {
 
 int vqs_qwen_bind_weights(vqs_qwen_handle* h, const vqs_weight_desc* descs, int32_t n, void* d_packed, size_t packed_bytes,
                           void* stream) {
-    if (!h || !descs || n <= 0 || !d_packed) return VQS_ERR_INVALID;
-    h->w.clear();
-    for (int i = 0; i < n; ++i) {
-        if (!descs[i].name || !descs[i].d_data) return qfail(h, VQS_ERR_INVALID, "bind: null name or pointer");
-        h->w[descs[i].name] = WEnt{(const bf16_t*)descs[i].d_data, descs[i].numel};
-    }
+    if (!h) return VQS_ERR_INVALID;
+    if (!descs || n <= 0 || !d_packed) return fail(h, VQS_ERR_INVALID, "bind_weights: bad arguments");
+    VQS_RUN(vqs::set_weights(h, descs, n));
     size_t need = 0;
-    QRUN(pack(h, nullptr, &need, nullptr));
-    if (packed_bytes < need) return qfail(h, VQS_ERR_WORKSPACE, "bind: packed buffer too small");
-    QRUN(pack(h, (char*)d_packed, &need, (hipStream_t)stream));
+    VQS_RUN(pack(h, nullptr, &need, nullptr));
+    if (packed_bytes < need) return fail(h, VQS_ERR_WORKSPACE, "bind_weights: packed buffer too small");
+    VQS_RUN(pack(h, (char*)d_packed, &need, (hipStream_t)stream));
     // every weight the launch sequences read directly must exist
     const vqs_qwen_config& c = h->c;
     const bf16_t* dummy;
     for (int i = 0; i < c.v_depth; ++i) {
         const std::string p = "model.visual.blocks." + std::to_string(i) + ".";
-        QRUN(get_w(h, p + "norm1.weight", c.v_hidden, &dummy));
-        QRUN(get_w(h, p + "norm2.weight", c.v_hidden, &dummy));
-        QRUN(get_w(h, p + "attn.proj.bias", c.v_hidden, &dummy));
-        QRUN(get_w(h, p + "mlp.down_proj.bias", c.v_hidden, &dummy));
+        VQS_RUN(vqs::get_w(h, p + "norm1.weight", c.v_hidden, &dummy));
+        VQS_RUN(vqs::get_w(h, p + "norm2.weight", c.v_hidden, &dummy));
+        VQS_RUN(vqs::get_w(h, p + "attn.proj.bias", c.v_hidden, &dummy));
+        VQS_RUN(vqs::get_w(h, p + "mlp.down_proj.bias", c.v_hidden, &dummy));
     }
-    QRUN(get_w(h, "model.visual.merger.ln_q.weight", c.v_hidden, &dummy));
-    QRUN(get_w(h, "model.visual.merger.mlp.0.weight", (int64_t)h->merge_hidden * h->merge_hidden, &dummy));
-    QRUN(get_w(h, "model.visual.merger.mlp.0.bias", h->merge_hidden, &dummy));
-    QRUN(get_w(h, "model.visual.merger.mlp.2.weight", (int64_t)c.v_out_hidden * h->merge_hidden, &dummy));
-    QRUN(get_w(h, "model.visual.merger.mlp.2.bias", c.v_out_hidden, &dummy));
-    QRUN(get_w(h, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * c.t_hidden, &dummy));
+    VQS_RUN(vqs::get_w(h, "model.visual.merger.ln_q.weight", c.v_hidden, &dummy));
+    VQS_RUN(vqs::get_w(h, "model.visual.merger.mlp.0.weight", (int64_t)h->merge_hidden * h->merge_hidden, &dummy));
+    VQS_RUN(vqs::get_w(h, "model.visual.merger.mlp.0.bias", h->merge_hidden, &dummy));
+    VQS_RUN(vqs::get_w(h, "model.visual.merger.mlp.2.weight", (int64_t)c.v_out_hidden * h->merge_hidden, &dummy));
+    VQS_RUN(vqs::get_w(h, "model.visual.merger.mlp.2.bias", c.v_out_hidden, &dummy));
+    VQS_RUN(vqs::get_w(h, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * c.t_hidden, &dummy));
     for (int i = 0; i < c.t_layers; ++i) {
         const std::string p = "model.language_model.layers." + std::to_string(i) + ".";
-        QRUN(get_w(h, p + "input_layernorm.weight", c.t_hidden, &dummy));
-        QRUN(get_w(h, p + "post_attention_layernorm.weight", c.t_hidden, &dummy));
+        VQS_RUN(vqs::get_w(h, p + "input_layernorm.weight", c.t_hidden, &dummy));
+        VQS_RUN(vqs::get_w(h, p + "post_attention_layernorm.weight", c.t_hidden, &dummy));
     }
-    QRUN(get_w(h, "model.language_model.norm.weight", c.t_hidden, &dummy));
-    QRUN(get_w(h, "lm_head.weight", (int64_t)c.t_vocab * c.t_hidden, &dummy));
+    VQS_RUN(vqs::get_w(h, "model.language_model.norm.weight", c.t_hidden, &dummy));
+    VQS_RUN(vqs::get_w(h, "lm_head.weight", (int64_t)c.t_vocab * c.t_hidden, &dummy));
     h->fp16_active = 0;
-    if (h->fp16_req) QRUN(compute_ranges(h, (hipStream_t)stream));
+    if (h->fp16_req) VQS_RUN(compute_ranges(h, (hipStream_t)stream));
     h->bound = true;
     return VQS_OK;
 }
@@ -793,43 +650,43 @@ int vqs_qwen_encode_vision(vqs_qwen_handle* h, const void* d_patches, int32_t N,
                            const float* d_sin_w, const float* d_cos_f, const float* d_sin_f, int32_t Np, int32_t win_len,
                            int32_t frame_len, void* d_merged, void* d_ws, size_t ws_bytes, void* stream) {
     if (!h) return VQS_ERR_INVALID;
-    if (!h->bound) return qfail(h, VQS_ERR_STATE, "encode_vision: weights not bound");
+    if (!h->bound) return fail(h, VQS_ERR_STATE, "encode_vision: weights not bound");
     if (!d_patches || !d_row_map || !d_inv_row || !d_win_valid || !d_cell_inv || !d_cos_w || !d_sin_w || !d_cos_f || !d_sin_f ||
         !d_merged || !d_ws)
-        return qfail(h, VQS_ERR_INVALID, "encode_vision: null argument");
+        return fail(h, VQS_ERR_INVALID, "encode_vision: null argument");
     const vqs_qwen_config& c = h->c;
     if (N <= 0 || Np < N || N % c.v_merge_unit || win_len <= 0 || frame_len <= 0 || Np % win_len || N % frame_len ||
         win_len % c.v_merge_unit)
-        return qfail(h, VQS_ERR_INVALID, "encode_vision: need N % merge_unit == 0, Np % win_len == 0, N % frame_len == 0");
+        return fail(h, VQS_ERR_INVALID, "encode_vision: need N % merge_unit == 0, Np % win_len == 0, N % frame_len == 0");
     const VisWs w = carve_vision(h, (char*)d_ws, N, Np);
-    if (ws_bytes < w.total) return qfail(h, VQS_ERR_WORKSPACE, "encode_vision: workspace too small");
+    if (ws_bytes < w.total) return fail(h, VQS_ERR_WORKSPACE, "encode_vision: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int VH = c.v_hidden, VNH = c.v_heads, VPK = VNH * HDP, NC = N / c.v_merge_unit;
     const float scale = 1.0f / sqrtf((float)h->v_hd);
 
     // patch embed = matmul over the flattened receptive field (K padded to 64), then the window permutation into the
     // padded windowed layout (slots of partial windows are zero rows)
-    QHIP(h, vqs::launch_gather_rows_bf16((const bf16_t*)d_patches, nullptr, nullptr, w.patches, N, c.v_patch_dim, c.v_patch_dim, h->v_kpatch, st), "pad patches");
+    VQS_HIP(h, vqs::launch_gather_rows_bf16((const bf16_t*)d_patches, nullptr, nullptr, w.patches, N, c.v_patch_dim, c.v_patch_dim, h->v_kpatch, st), "pad patches");
     {
-        GCall g{w.patches, h->patch_w, w.pre};
+        GemmCall g{w.patches, h->patch_w, w.pre};
         g.M = N; g.N = VH; g.K = h->v_kpatch; g.lda = h->v_kpatch; g.ldw = h->v_kpatch; g.ldc = VH; g.epi = vqs::EPI_F32;
-        QRUN(qgemm(h, g, st, "patch embed"));
+        VQS_RUN(run_gemm(h, g, {}, st, "patch embed"));
     }
-    QTAP("vis", -1, "pre", w.pre, (size_t)N * VH);
-    QHIP(h, vqs::launch_gather_rows_f32(w.pre, d_row_map, w.hidden, Np, VH, st), "window permutation");
-    QHIP(h, hipMemsetAsync(w.ff, 0, (size_t)Np * h->v_ffld * sizeof(bf16_t), st), "clear ff padding");
+    VQS_TAP("vis", -1, "pre", w.pre, (size_t)N * VH);
+    VQS_HIP(h, vqs::launch_gather_rows_f32(w.pre, d_row_map, w.hidden, Np, VH, st), "window permutation");
+    VQS_HIP(h, hipMemsetAsync(w.ff, 0, (size_t)Np * h->v_ffld * sizeof(bf16_t), st), "clear ff padding");
     const bool cp = h->v_compact;
     const int VAK = cp ? VH : VPK;       // width of the attention output = K of the proj GEMM
     if (cp)   // lanes [v_hd, 128) of every head slot: written by nobody, read by the attention kernel (q | k | v are contiguous)
-        QHIP(h, hipMemsetAsync(w.q, 0, (size_t)((char*)w.attn - (char*)w.q), st), "clear head padding");
+        VQS_HIP(h, hipMemsetAsync(w.q, 0, (size_t)((char*)w.attn - (char*)w.q), st), "clear head padding");
     // F: the range-safe fp16 forms (every 16-bit tensor below is fp16(T * sigma_T), sigma_T from the bind-time proof); else bf16
     const bool F = h->fp16_active != 0;
-    if (F && (win_len < 8 || frame_len < 8)) return qfail(h, VQS_ERR_INVALID, "encode_vision: the fp16 forms need windows and frames of >= 8 patches (option fp16 = 0 runs any)");
+    if (F && (win_len < 8 || frame_len < 8)) return fail(h, VQS_ERR_INVALID, "encode_vision: the fp16 forms need windows and frames of >= 8 patches (option fp16 = 0 runs any)");
     const vqs_qwen_handle::LayerSites one{};
     // RMSNorm whose pending deltas sit behind sd1 / sd2 and whose operand leaves behind so
     auto norm = [&](const bf16_t* d, const bf16_t* g, const bf16_t* d2, bool store, float eps, float sd1, float sd2, float so, const char* what) -> int {
-        if (F) QHIP(h, vqs::launch_rmsnorm_f16s(w.hidden, d, g, w.xn, Np, VH, eps, st, d2, store, 0, 1.0f / sd1, 1.0f / sd2, so), what);
-        else QHIP(h, vqs::launch_rmsnorm(w.hidden, d, g, w.xn, Np, VH, eps, st, d2, store), what);
+        if (F) VQS_HIP(h, vqs::launch_rmsnorm_f16s(w.hidden, d, g, w.xn, Np, VH, eps, st, d2, store, 0, 1.0f / sd1, 1.0f / sd2, so), what);
+        else VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, d, g, w.xn, Np, VH, eps, st, d2, store), what);
         return VQS_OK;
     };
 
@@ -838,110 +695,110 @@ int vqs_qwen_encode_vision(vqs_qwen_handle* h, const void* d_patches, int32_t N,
     float s_pend = 1.0f, s_pend_attn = 1.0f;     // their scales
     for (int i = 0; i < c.v_depth; ++i) {
         const std::string p = "model.visual.blocks." + std::to_string(i) + ".";
-        QW(n1, p + "norm1.weight", VH);
-        QW(n2, p + "norm2.weight", VH);
-        QW(pb, p + "attn.proj.bias", VH);
-        QW(db, p + "mlp.down_proj.bias", VH);
+        VQS_W(n1, p + "norm1.weight", VH);
+        VQS_W(n2, p + "norm2.weight", VH);
+        VQS_W(pb, p + "attn.proj.bias", VH);
+        VQS_W(db, p + "mlp.down_proj.bias", VH);
         const vqs_qwen_handle::LayerSites& sc = F ? h->v_sc[i] : one;
         const bool full = ((c.v_fullatt_mask >> i) & 1) != 0;
         // deferred store: norm2 normalises hidden + attention delta without writing the stream; the next norm1 (or the
         // merger norm) stores (hidden + attention delta) + mlp delta -- same fp32 sums, 22 instead of 24 B per element
-        QRUN(norm(pend_attn ? pend_attn : pend, n1, pend_attn ? pend : nullptr, true, c.v_eps, pend_attn ? s_pend_attn : s_pend, s_pend, sc.x0.sigma, "vision norm1"));
-        QTAP("vis", i, "h", w.hidden, (size_t)Np * VH);          // the fp32 stream this block starts from (norm1 stored it)
-        QTAP("vis", i, "xn0", w.xn, (size_t)Np * VH);
+        VQS_RUN(norm(pend_attn ? pend_attn : pend, n1, pend_attn ? pend : nullptr, true, c.v_eps, pend_attn ? s_pend_attn : s_pend, s_pend, sc.x0.sigma, "vision norm1"));
+        VQS_TAP("vis", i, "h", w.hidden, (size_t)Np * VH);          // the fp32 stream this block starts from (norm1 stored it)
+        VQS_TAP("vis", i, "xn0", w.xn, (size_t)Np * VH);
         // window blocks run on the padded windowed layout (every window = win_len slots, d_win_valid of them real);
         // full-attention blocks on a frame-compact copy (original patch order), scattered back afterwards
         const bf16_t* xin = w.xn;
         int rows = Np, S = win_len;
         if (full) {
-            QHIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, d_inv_row, w.xc, N, VH, VH, VH, st), "compact frame rows");
+            VQS_HIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, d_inv_row, w.xc, N, VH, VH, VH, st), "compact frame rows");
             xin = w.xc; rows = N; S = frame_len;
         }
         const int Bseg = rows / S;
         {
-            GCall g{xin, F ? h->v_qkv_h[i] : h->v_qkv_w[i], nullptr};
+            GemmCall g{xin, F ? h->v_qkv_h[i] : h->v_qkv_w[i], nullptr};
             g.bias = h->v_qkv_b[i];
             g.M = rows; g.N = cp ? 3 * VH : 3 * VPK; g.K = VH; g.lda = VH; g.ldw = VH; g.epi = vqs::EPI_HEADS;
             g.S = S; g.H = VNH; g.inner = cp ? VH : VPK; g.hd = HDP; g.hd_src = cp ? h->v_hd : 0;
             g.heads[0] = w.q; g.heads[1] = w.k; g.heads[2] = w.v;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x0.sigma; g.out_scale = sc.qkv.sigma; }
-            QRUN(qgemm(h, g, st, "vision qkv"));
+            VQS_RUN(run_gemm(h, g, {}, st, "vision qkv"));
         }
-        QTAP("vis", i, "q0", w.q, (size_t)rows * VPK);           // projection output, before the rotary embedding
-        QTAP("vis", i, "k0", w.k, (size_t)rows * VPK);
-        QHIP(h, vqs::launch_rope_qk(w.q, w.k, full ? d_cos_f : d_cos_w, full ? d_sin_f : d_sin_w, Bseg, VNH, VNH, S, HDP, h->v_hd / 2, st, F), "vision rope");
-        QTAP("vis", i, "q", w.q, (size_t)rows * VPK);            // after the rotary embedding, head-major [Bseg, heads, S, 128]
-        QTAP("vis", i, "k", w.k, (size_t)rows * VPK);
-        QTAP("vis", i, "v", w.v, (size_t)rows * VPK);
+        VQS_TAP("vis", i, "q0", w.q, (size_t)rows * VPK);           // projection output, before the rotary embedding
+        VQS_TAP("vis", i, "k0", w.k, (size_t)rows * VPK);
+        VQS_HIP(h, vqs::launch_rope_qk(w.q, w.k, full ? d_cos_f : d_cos_w, full ? d_sin_f : d_sin_w, Bseg, VNH, VNH, S, HDP, h->v_hd / 2, st, F), "vision rope");
+        VQS_TAP("vis", i, "q", w.q, (size_t)rows * VPK);            // after the rotary embedding, head-major [Bseg, heads, S, 128]
+        VQS_TAP("vis", i, "k", w.k, (size_t)rows * VPK);
+        VQS_TAP("vis", i, "v", w.v, (size_t)rows * VPK);
         {   // q and k sit behind sigma_qkv each: the scores' scale takes 1 / sigma^2; the output inherits v's sigma
             vqs::AttnParams a{w.q, w.k, w.v, w.attn, nullptr, full ? nullptr : d_win_valid, Bseg, VNH, S, scale / (sc.qkv.sigma * sc.qkv.sigma)};
             a.hd = HDP; a.out_hd = cp ? h->v_hd : 0; a.f16 = F ? 1 : 0;
-            QHIP(h, vqs::launch_attention(a, st), "vision attention");
+            VQS_HIP(h, vqs::launch_attention(a, st), "vision attention");
         }
-        QTAP("vis", i, "attn", w.attn, (size_t)rows * VAK);
+        VQS_TAP("vis", i, "attn", w.attn, (size_t)rows * VAK);
         {
-            GCall g{w.attn, F ? h->v_proj_h[i] : h->v_proj_w[i], full ? (void*)w.dc : (void*)w.delta};
+            GemmCall g{w.attn, F ? h->v_proj_h[i] : h->v_proj_w[i], full ? (void*)w.dc : (void*)w.delta};
             g.bias = pb;
             g.M = rows; g.N = VH; g.K = VAK; g.lda = VAK; g.ldw = VAK; g.ldc = VH; g.epi = vqs::EPI_BF16;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.qkv.sigma; g.out_scale = sc.dattn.sigma; }
-            QRUN(qgemm(h, g, st, "vision proj"));
+            VQS_RUN(run_gemm(h, g, {}, st, "vision proj"));
         }
         if (full)
-            QHIP(h, vqs::launch_gather_rows_bf16(w.dc, nullptr, d_row_map, w.delta, Np, VH, VH, VH, st), "scatter frame rows back");
-        QTAP("vis", i, "d_attn", w.delta, (size_t)Np * VH);
-        QRUN(norm(w.delta, n2, nullptr, false, c.v_eps, sc.dattn.sigma, 1.0f, sc.x1.sigma, "vision norm2"));
-        QTAP("vis", i, "xn1", w.xn, (size_t)Np * VH);
+            VQS_HIP(h, vqs::launch_gather_rows_bf16(w.dc, nullptr, d_row_map, w.delta, Np, VH, VH, VH, st), "scatter frame rows back");
+        VQS_TAP("vis", i, "d_attn", w.delta, (size_t)Np * VH);
+        VQS_RUN(norm(w.delta, n2, nullptr, false, c.v_eps, sc.dattn.sigma, 1.0f, sc.x1.sigma, "vision norm2"));
+        VQS_TAP("vis", i, "xn1", w.xn, (size_t)Np * VH);
         pend_attn = w.delta; s_pend_attn = sc.dattn.sigma;
         {
-            GCall g{w.xn, F ? h->v_gu_h[i] : h->v_gu_w[i], w.ff};
+            GemmCall g{w.xn, F ? h->v_gu_h[i] : h->v_gu_w[i], w.ff};
             g.bias = h->v_gu_b[i];
             g.M = Np; g.N = 2 * h->v_mlp_p; g.K = VH; g.lda = VH; g.ldw = VH; g.ldc = h->v_ffld; g.epi = vqs::EPI_GATED; g.gate_act = 1;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x1.sigma; g.out_scale = sc.act.sigma; }
-            QRUN(qgemm(h, g, st, "vision gate|up"));
+            VQS_RUN(run_gemm(h, g, {}, st, "vision gate|up"));
         }
-        QTAP("vis", i, "ff", w.ff, (size_t)Np * h->v_ffld);
+        VQS_TAP("vis", i, "ff", w.ff, (size_t)Np * h->v_ffld);
         {
-            GCall g{w.ff, F ? h->v_down_h[i] : h->v_down_w[i], w.delta2};
+            GemmCall g{w.ff, F ? h->v_down_h[i] : h->v_down_w[i], w.delta2};
             g.bias = db;
             g.M = Np; g.N = VH; g.K = h->v_ffld; g.lda = h->v_ffld; g.ldw = h->v_ffld; g.ldc = VH; g.epi = vqs::EPI_BF16;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.act.sigma; g.out_scale = sc.dmlp.sigma; }
-            QRUN(qgemm(h, g, st, "vision down"));
+            VQS_RUN(run_gemm(h, g, {}, st, "vision down"));
             pend = w.delta2; s_pend = sc.dmlp.sigma;
         }
-        QTAP("vis", i, "d_mlp", w.delta2, (size_t)Np * VH);
+        VQS_TAP("vis", i, "d_mlp", w.delta2, (size_t)Np * VH);
     }
     // merger: RMSNorm, the 4 patches of a cell (consecutive rows in the windowed layout) concatenated, Linear-GELU-Linear,
     // then original cell order (padding cells are simply never gathered)
-    QW(lnq, "model.visual.merger.ln_q.weight", VH);
-    QW(m0w, "model.visual.merger.mlp.0.weight", (int64_t)h->merge_hidden * h->merge_hidden);
-    QW(m0b, "model.visual.merger.mlp.0.bias", h->merge_hidden);
-    QW(m2w, "model.visual.merger.mlp.2.weight", (int64_t)c.v_out_hidden * h->merge_hidden);
-    QW(m2b, "model.visual.merger.mlp.2.bias", c.v_out_hidden);
+    VQS_W(lnq, "model.visual.merger.ln_q.weight", VH);
+    VQS_W(m0w, "model.visual.merger.mlp.0.weight", (int64_t)h->merge_hidden * h->merge_hidden);
+    VQS_W(m0b, "model.visual.merger.mlp.0.bias", h->merge_hidden);
+    VQS_W(m2w, "model.visual.merger.mlp.2.weight", (int64_t)c.v_out_hidden * h->merge_hidden);
+    VQS_W(m2b, "model.visual.merger.mlp.2.bias", c.v_out_hidden);
     const int NCp = Np / c.v_merge_unit;
     const float s_mx = F ? h->m_x.sigma : 1.0f, s_mid = F ? h->m_mid.sigma : 1.0f, s_mo = F ? h->m_out.sigma : 1.0f;
-    QRUN(norm(pend_attn ? pend_attn : pend, lnq, pend_attn ? pend : nullptr, true, 1e-6f, pend_attn ? s_pend_attn : s_pend, s_pend, s_mx, "merger norm"));
-    QTAP("vis", -1, "h_out", w.hidden, (size_t)Np * VH);
-    QTAP("vis", -1, "xnm", w.xn, (size_t)Np * VH);
+    VQS_RUN(norm(pend_attn ? pend_attn : pend, lnq, pend_attn ? pend : nullptr, true, 1e-6f, pend_attn ? s_pend_attn : s_pend, s_pend, s_mx, "merger norm"));
+    VQS_TAP("vis", -1, "h_out", w.hidden, (size_t)Np * VH);
+    VQS_TAP("vis", -1, "xnm", w.xn, (size_t)Np * VH);
     {
-        GCall g{w.xn, F ? h->m0_h : m0w, w.mid};
+        GemmCall g{w.xn, F ? h->m0_h : m0w, w.mid};
         g.bias = m0b;
         g.M = NCp; g.N = h->merge_hidden; g.K = h->merge_hidden; g.lda = h->merge_hidden; g.ldw = h->merge_hidden; g.ldc = h->merge_hidden;
         g.epi = vqs::EPI_BF16_GELU;
         if (F) { g.f16 = 3; g.acc_scale = 1.0f / s_mx; g.out_scale = s_mid; }
-        QRUN(qgemm(h, g, st, "merger mlp.0"));
+        VQS_RUN(run_gemm(h, g, {}, st, "merger mlp.0"));
     }
-    QTAP("vis", -1, "mid", w.mid, (size_t)NCp * h->merge_hidden);
+    VQS_TAP("vis", -1, "mid", w.mid, (size_t)NCp * h->merge_hidden);
     {
-        GCall g{w.mid, F ? h->m2_h : m2w, w.merged_w};
+        GemmCall g{w.mid, F ? h->m2_h : m2w, w.merged_w};
         g.bias = m2b;
         g.M = NCp; g.N = c.v_out_hidden; g.K = h->merge_hidden; g.lda = h->merge_hidden; g.ldw = h->merge_hidden; g.ldc = c.v_out_hidden;
         g.epi = vqs::EPI_BF16;
         if (F) { g.f16 = 3; g.acc_scale = 1.0f / s_mid; g.out_scale = s_mo; }
-        QRUN(qgemm(h, g, st, "merger mlp.2"));
+        VQS_RUN(run_gemm(h, g, {}, st, "merger mlp.2"));
     }
-    QTAP("vis", -1, "merged_w", w.merged_w, (size_t)NCp * c.v_out_hidden);
+    VQS_TAP("vis", -1, "merged_w", w.merged_w, (size_t)NCp * c.v_out_hidden);
     // d_merged leaves in the handle's operand format: bf16, or (fp16 forms) fp16 behind the merger's output scale -- vqs_qwen_score reads it back the same way
-    QHIP(h, vqs::launch_gather_rows_bf16(w.merged_w, nullptr, d_cell_inv, (bf16_t*)d_merged, NC, c.v_out_hidden, c.v_out_hidden,
+    VQS_HIP(h, vqs::launch_gather_rows_bf16(w.merged_w, nullptr, d_cell_inv, (bf16_t*)d_merged, NC, c.v_out_hidden, c.v_out_hidden,
                                           c.v_out_hidden, st), "undo window permutation");
     return VQS_OK;
 }
@@ -973,28 +830,12 @@ inline size_t kv_slab(const vqs_qwen_handle* h, int B, int Lmax) { return (size_
 int tail_linear(vqs_qwen_handle* h, const bf16_t* A2, int lda, const bf16_t* W, int ldw, const bf16_t* bias, int rows, int N, int K, int mode,
                 void* out, int ld_out, long long out_plane, const TxtWs& w, hipStream_t st, const char* what) {
     const int sk = decode_slices(N, K);
-    if ((size_t)sk * 2 * rows * N * sizeof(float) > w.t_part_bytes) return qfail(h, VQS_ERR_WORKSPACE, std::string(what) + ": tail scratch too small");
-    vqs::GemmParams p{};
-    p.A = A2; p.W = W; p.C = w.t_part; p.bias = nullptr; p.resid = nullptr;
-    p.M = 2 * rows; p.N = N; p.K = K / sk; p.lda = lda; p.ldw = ldw; p.ldc = N;
-    p.S = 1; p.H = 0; p.inner = 1;
-    p.batch = sk; p.sA = K / sk; p.sW = K / sk; p.sC = (long long)2 * rows * N;
-    if (h->prof) {
-        while (h->ev.size() < h->ev_used + 2) {
-            hipEvent_t e;
-            QHIP(h, hipEventCreate(&e), "hipEventCreate");
-            h->ev.push_back(e);
-        }
-        QHIP(h, hipEventRecord(h->ev[h->ev_used], st), "hipEventRecord");
-    }
-    QHIP(h, vqs::launch_gemm(p, vqs::EPI_F32, 3, st), std::string("gemm ") + what);
-    if (h->prof) {
-        QHIP(h, hipEventRecord(h->ev[h->ev_used + 1], st), "hipEventRecord");
-        h->ev_used += 2;
-        h->prof_flops += 2.0 * 2.0 * (double)rows * (double)N * (double)K;
-        h->prof_bytes += 2.0 * (2.0 * (double)rows + (double)N) * (double)K + 4.0 * (double)sk * 2.0 * (double)rows * (double)N;
-    }
-    QHIP(h, vqs::launch_sum_planes(w.t_part, sk, (long long)2 * rows * N, rows, N, N, mode, out, ld_out, out_plane, st, bias,
+    if ((size_t)sk * 2 * rows * N * sizeof(float) > w.t_part_bytes) return fail(h, VQS_ERR_WORKSPACE, std::string(what) + ": tail scratch too small");
+    GemmCall g{A2, W, w.t_part};      // K slices as batch entries, fp32 partials
+    g.M = 2 * rows; g.N = N; g.K = K / sk; g.lda = lda; g.ldw = ldw; g.ldc = N; g.epi = vqs::EPI_F32;
+    g.batch = sk; g.sA = K / sk; g.sW = K / sk; g.sC = (long long)2 * rows * N;
+    VQS_RUN(run_gemm(h, g, {}, st, what));
+    VQS_HIP(h, vqs::launch_sum_planes(w.t_part, sk, (long long)2 * rows * N, rows, N, N, mode, out, ld_out, out_plane, st, bias,
                                    mode == vqs::SUM_GATED_SPLIT ? 1 : 0), std::string("sum ") + what);
     return VQS_OK;
 }
@@ -1010,19 +851,19 @@ int tail_layer(vqs_qwen_handle* h, const TxtWs& w, int i, const bf16_t* ln1, con
         float* th = w.t_h + (size_t)c0 * TH;
         float* td = w.t_delta + (size_t)c0 * TH;
         // ---- attention sub-layer
-        QHIP(h, vqs::launch_rmsnorm_split(th, first ? nullptr : td, ln1, w.t_xn, (long long)rows * TH, rows, TH, c.t_eps, st), "tail input_layernorm");
-        QRUN(tail_linear(h, w.t_xn, TH, h->t_qkv_w[i], TH, h->t_qkv_b[i], rows, QN, TH, vqs::SUM_F32, w.t_qkv, QN, 0, w, st, "tail qkv"));
-        QHIP(h, vqs::launch_qwen_tail_rope_q(w.t_qkv, QN, d_cos, d_sin, d_last_row + c0, w.t_q, rows, c.t_heads, HDP, h->t_hd / 2, st), "tail rope");
+        VQS_HIP(h, vqs::launch_rmsnorm_split(th, first ? nullptr : td, ln1, w.t_xn, (long long)rows * TH, rows, TH, c.t_eps, st), "tail input_layernorm");
+        VQS_RUN(tail_linear(h, w.t_xn, TH, h->t_qkv_w[i], TH, h->t_qkv_b[i], rows, QN, TH, vqs::SUM_F32, w.t_qkv, QN, 0, w, st, "tail qkv"));
+        VQS_HIP(h, vqs::launch_qwen_tail_rope_q(w.t_qkv, QN, d_cos, d_sin, d_last_row + c0, w.t_q, rows, c.t_heads, HDP, h->t_hd / 2, st), "tail rope");
         // kv_f16: the layer's K / V are the fp16 prefill's tensors behind kv_sigma (the tail's own q is in true units)
-        QHIP(h, vqs::launch_qwen_tail_attn(w.t_q, w.k + (size_t)c0 * L * IKV, w.v + (size_t)c0 * L * IKV, d_seq_len + c0, w.t_attn, (long long)rows * IQ, rows,
+        VQS_HIP(h, vqs::launch_qwen_tail_attn(w.t_q, w.k + (size_t)c0 * L * IKV, w.v + (size_t)c0 * L * IKV, d_seq_len + c0, w.t_attn, (long long)rows * IQ, rows,
                                            c.t_heads, c.t_kv_heads, L, scale / kv_sigma, st, kv_f16, 1.0f / kv_sigma), "tail attention");
-        QRUN(tail_linear(h, w.t_attn, IQ, h->t_o_w[i], IQ, nullptr, rows, TH, IQ, vqs::SUM_F32, td, TH, 0, w, st, "tail o_proj"));
+        VQS_RUN(tail_linear(h, w.t_attn, IQ, h->t_o_w[i], IQ, nullptr, rows, TH, IQ, vqs::SUM_F32, td, TH, 0, w, st, "tail o_proj"));
         // ---- gated FFN
-        QHIP(h, vqs::launch_rmsnorm_split(th, td, ln2, w.t_xn, (long long)rows * TH, rows, TH, c.t_eps, st), "tail post_attention_layernorm");
-        QHIP(h, hipMemsetAsync(w.t_ff, 0, (size_t)2 * rows * h->t_ffld * sizeof(bf16_t), st), "tail clear ff padding");
-        QRUN(tail_linear(h, w.t_xn, TH, h->t_gu_w[i], h->t_xld, nullptr, rows, 2 * h->t_mlp_p, TH, vqs::SUM_GATED_SPLIT, w.t_ff, h->t_ffld,
+        VQS_HIP(h, vqs::launch_rmsnorm_split(th, td, ln2, w.t_xn, (long long)rows * TH, rows, TH, c.t_eps, st), "tail post_attention_layernorm");
+        VQS_HIP(h, hipMemsetAsync(w.t_ff, 0, (size_t)2 * rows * h->t_ffld * sizeof(bf16_t), st), "tail clear ff padding");
+        VQS_RUN(tail_linear(h, w.t_xn, TH, h->t_gu_w[i], h->t_xld, nullptr, rows, 2 * h->t_mlp_p, TH, vqs::SUM_GATED_SPLIT, w.t_ff, h->t_ffld,
                          (long long)rows * h->t_ffld, w, st, "tail gate|up"));
-        QRUN(tail_linear(h, w.t_ff, h->t_ffld, h->t_down_w[i], h->t_ffld, nullptr, rows, TH, h->t_ffld, vqs::SUM_F32, td, TH, 0, w, st, "tail down_proj"));
+        VQS_RUN(tail_linear(h, w.t_ff, h->t_ffld, h->t_down_w[i], h->t_ffld, nullptr, rows, TH, h->t_ffld, vqs::SUM_F32, td, TH, 0, w, st, "tail down_proj"));
     }
     return VQS_OK;
 }
@@ -1033,8 +874,8 @@ int tail_head(vqs_qwen_handle* h, const TxtWs& w, const bf16_t* fin, const bf16_
     const int TH = c.t_hidden;
     for (int c0 = 0; c0 < B; c0 += TAIL_ROWS) {
         const int rows = std::min(TAIL_ROWS, B - c0);
-        QHIP(h, vqs::launch_rmsnorm_split(w.t_h + (size_t)c0 * TH, w.t_delta + (size_t)c0 * TH, fin, w.t_xn, (long long)rows * TH, rows, TH, c.t_eps, st), "tail final norm");
-        QRUN(tail_linear(h, w.t_xn, TH, head, TH, nullptr, rows, c.t_vocab, TH, vqs::SUM_F32, d_logits + (size_t)c0 * c.t_vocab, c.t_vocab, 0, w, st, "tail lm_head"));
+        VQS_HIP(h, vqs::launch_rmsnorm_split(w.t_h + (size_t)c0 * TH, w.t_delta + (size_t)c0 * TH, fin, w.t_xn, (long long)rows * TH, rows, TH, c.t_eps, st), "tail final norm");
+        VQS_RUN(tail_linear(h, w.t_xn, TH, head, TH, nullptr, rows, c.t_vocab, TH, vqs::SUM_F32, d_logits + (size_t)c0 * c.t_vocab, c.t_vocab, 0, w, st, "tail lm_head"));
     }
     return VQS_OK;
 }
@@ -1044,31 +885,31 @@ int score_impl(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_input_
                const int32_t* d_seq_len, const int32_t* d_last_row, const float* d_cos, const float* d_sin, int32_t B,
                int32_t L, float* d_logits, void* d_ws, size_t ws_bytes, void* stream, void* d_kv, int32_t Lmax) {
     if (!h) return VQS_ERR_INVALID;
-    if (!h->bound) return qfail(h, VQS_ERR_STATE, "score: weights not bound");
+    if (!h->bound) return fail(h, VQS_ERR_STATE, "score: weights not bound");
     if (!d_merged || !d_input_ids || !d_vis_slot || !d_seq_len || !d_last_row || !d_cos || !d_sin || !d_logits || !d_ws)
-        return qfail(h, VQS_ERR_INVALID, "score: null argument");
-    if (B <= 0 || L <= 0) return qfail(h, VQS_ERR_INVALID, "score: need B > 0, L > 0");
+        return fail(h, VQS_ERR_INVALID, "score: null argument");
+    if (B <= 0 || L <= 0) return fail(h, VQS_ERR_INVALID, "score: need B > 0, L > 0");
     const vqs_qwen_config& c = h->c;
     const TxtWs w = carve_text(h, (char*)d_ws, B, L);
-    if (ws_bytes < w.total) return qfail(h, VQS_ERR_WORKSPACE, "score: workspace too small");
+    if (ws_bytes < w.total) return fail(h, VQS_ERR_WORKSPACE, "score: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int TH = c.t_hidden, M = B * L, IQ = h->t_iq, IKV = h->t_ikv, XLD = h->t_xld;
     const float scale = 1.0f / sqrtf((float)h->t_hd);
-    QW(embed, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * TH);
+    VQS_W(embed, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * TH);
     // F: the range-safe fp16 forms (bind-time proof; every 16-bit tensor is fp16(T * sigma_T)); d_merged arrives in the same format
     const bool F = h->fp16_active != 0;
-    if (F && L < 8) return qfail(h, VQS_ERR_INVALID, "score: the fp16 forms need L >= 8 (option fp16 = 0 runs any)");
-    QHIP(h, vqs::launch_qwen_embed(d_input_ids, d_vis_slot, embed, (const bf16_t*)d_merged, w.hidden, M, TH, c.t_vocab, st, F, F ? 1.0f / h->m_out.sigma : 1.0f), "embed + splice");
-    QHIP(h, hipMemsetAsync(w.ff, 0, (size_t)M * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
-    QTAP("txt", -1, "emb", w.hidden, (size_t)M * TH);
+    if (F && L < 8) return fail(h, VQS_ERR_INVALID, "score: the fp16 forms need L >= 8 (option fp16 = 0 runs any)");
+    VQS_HIP(h, vqs::launch_qwen_embed(d_input_ids, d_vis_slot, embed, (const bf16_t*)d_merged, w.hidden, M, TH, c.t_vocab, st, F, F ? 1.0f / h->m_out.sigma : 1.0f), "embed + splice");
+    VQS_HIP(h, hipMemsetAsync(w.ff, 0, (size_t)M * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
+    VQS_TAP("txt", -1, "emb", w.hidden, (size_t)M * TH);
     const bool tail = h->tail_precise != 0 && (c.t_vocab % 4) == 0 && (c.t_hidden % 4) == 0;
     if (tail)      // the tail's starting state: the embedding rows of the last positions (fp32 copies of bf16 values: exact)
-        QHIP(h, vqs::launch_gather_rows_f32(w.hidden, d_last_row, w.t_h, B, TH, TH, st), "tail embed rows");
+        VQS_HIP(h, vqs::launch_gather_rows_f32(w.hidden, d_last_row, w.t_h, B, TH, TH, st), "tail embed rows");
     const vqs_qwen_handle::LayerSites one{};
     const bool rope_in_gemm = F && h->rope_fused != 0 && h->t_hd == HDP;      // K12: 128-lane heads, scaled fp16 family (gemm_quad.inc ROPE)
     auto norm = [&](const bf16_t* d, const bf16_t* g, const bf16_t* d2, bool store, float sd1, float sd2, float so, bool out_bf16, const char* what) -> int {
-        if (F) QHIP(h, vqs::launch_rmsnorm_f16s(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD, 1.0f / sd1, 1.0f / sd2, so, out_bf16), what);
-        else QHIP(h, vqs::launch_rmsnorm(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD), what);
+        if (F) VQS_HIP(h, vqs::launch_rmsnorm_f16s(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD, 1.0f / sd1, 1.0f / sd2, so, out_bf16), what);
+        else VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD), what);
         return VQS_OK;
     };
 
@@ -1077,92 +918,92 @@ int score_impl(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_input_
     float s_pend = 1.0f, s_pend_attn = 1.0f;
     for (int i = 0; i < c.t_layers; ++i) {
         const std::string p = "model.language_model.layers." + std::to_string(i) + ".";
-        QW(ln1, p + "input_layernorm.weight", TH);
-        QW(ln2, p + "post_attention_layernorm.weight", TH);
+        VQS_W(ln1, p + "input_layernorm.weight", TH);
+        VQS_W(ln2, p + "post_attention_layernorm.weight", TH);
         const vqs_qwen_handle::LayerSites& sc = F ? h->t_sc[i] : one;
-        QRUN(norm(pend_attn ? pend_attn : pend, ln1, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, sc.x0.sigma, false, "input_layernorm"));
-        QTAP("txt", i, "h", w.hidden, (size_t)M * TH);            // the fp32 stream this layer starts from (input_layernorm stored it)
-        QRUN(qtap2d(h, "txt", i, "xn0", w.xn, TH, M, XLD, st));
+        VQS_RUN(norm(pend_attn ? pend_attn : pend, ln1, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, sc.x0.sigma, false, "input_layernorm"));
+        VQS_TAP("txt", i, "h", w.hidden, (size_t)M * TH);            // the fp32 stream this layer starts from (input_layernorm stored it)
+        VQS_RUN(tap2d(h, "txt", i, "xn0", w.xn, TH, M, XLD, st));
         {
-            GCall g{w.xn, F ? h->t_qkv_h[i] : h->t_qkv_w[i], nullptr};
+            GemmCall g{w.xn, F ? h->t_qkv_h[i] : h->t_qkv_w[i], nullptr};
             g.bias = h->t_qkv_b[i];
             g.M = M; g.N = IQ + 2 * IKV; g.K = TH; g.lda = XLD; g.ldw = TH; g.epi = vqs::EPI_HEADS;
             g.S = L; g.H = c.t_heads; g.inner = IQ; g.hd = HDP; g.inner_kv = IKV; g.Hkv = c.t_kv_heads;
             g.heads[0] = w.q; g.heads[1] = w.k; g.heads[2] = w.v;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x0.sigma; g.out_scale = sc.qkv.sigma; }
             if (rope_in_gemm) { g.rope_cos = d_cos; g.rope_sin = d_sin; }
-            QRUN(qgemm(h, g, st, "qkv"));
+            VQS_RUN(run_gemm(h, g, {}, st, "qkv"));
         }
         if (!rope_in_gemm) {
-            QTAP("txt", i, "q0", w.q, (size_t)M * IQ);            // projection output, before the rotary embedding
-            QTAP("txt", i, "k0", w.k, (size_t)M * IKV);
-            QHIP(h, vqs::launch_rope_qk(w.q, w.k, d_cos, d_sin, B, c.t_heads, c.t_kv_heads, L, HDP, h->t_hd / 2, st, F), "rope");
+            VQS_TAP("txt", i, "q0", w.q, (size_t)M * IQ);            // projection output, before the rotary embedding
+            VQS_TAP("txt", i, "k0", w.k, (size_t)M * IKV);
+            VQS_HIP(h, vqs::launch_rope_qk(w.q, w.k, d_cos, d_sin, B, c.t_heads, c.t_kv_heads, L, HDP, h->t_hd / 2, st, F), "rope");
         }
-        QTAP("txt", i, "q", w.q, (size_t)M * IQ);                 // after the rotary embedding, head-major [B, heads, L, 128]
-        QTAP("txt", i, "k", w.k, (size_t)M * IKV);
-        QTAP("txt", i, "v", w.v, (size_t)M * IKV);
+        VQS_TAP("txt", i, "q", w.q, (size_t)M * IQ);                 // after the rotary embedding, head-major [B, heads, L, 128]
+        VQS_TAP("txt", i, "k", w.k, (size_t)M * IKV);
+        VQS_TAP("txt", i, "v", w.v, (size_t)M * IKV);
         if (d_kv) {   // rows [b, head, 0 .. L) of the cache slabs (pitch Lmax positions); the cache (and the decode step) is bf16 in true units
             bf16_t* kc = (bf16_t*)d_kv + (size_t)(2 * i) * kv_slab(h, B, Lmax);
             bf16_t* vc = kc + kv_slab(h, B, Lmax);
             const size_t wb = (size_t)L * HDP * sizeof(bf16_t), pb = (size_t)Lmax * HDP * sizeof(bf16_t), nr = (size_t)B * c.t_kv_heads;
             if (F) {
-                if (nr > 65535) return qfail(h, VQS_ERR_INVALID, "prefill: B * kv_heads exceeds 65535");
-                QHIP(h, vqs::launch_f16_to_bf16_rows(w.k, kc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep K");
-                QHIP(h, vqs::launch_f16_to_bf16_rows(w.v, vc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep V");
+                if (nr > 65535) return fail(h, VQS_ERR_INVALID, "prefill: B * kv_heads exceeds 65535");
+                VQS_HIP(h, vqs::launch_f16_to_bf16_rows(w.k, kc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep K");
+                VQS_HIP(h, vqs::launch_f16_to_bf16_rows(w.v, vc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep V");
             } else {
-                QHIP(h, hipMemcpy2DAsync(kc, pb, w.k, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep K");
-                QHIP(h, hipMemcpy2DAsync(vc, pb, w.v, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep V");
+                VQS_HIP(h, hipMemcpy2DAsync(kc, pb, w.k, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep K");
+                VQS_HIP(h, hipMemcpy2DAsync(vc, pb, w.v, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep V");
             }
         }
         {
             vqs::AttnParams a{w.q, w.k, w.v, w.attn, nullptr, d_seq_len, B, c.t_heads, L, scale / (sc.qkv.sigma * sc.qkv.sigma)};
             a.hd = HDP; a.Hkv = c.t_kv_heads; a.causal = 1; a.f16 = F ? 1 : 0;
-            QHIP(h, vqs::launch_attention(a, st), "attention");
+            VQS_HIP(h, vqs::launch_attention(a, st), "attention");
         }
-        QTAP("txt", i, "attn", w.attn, (size_t)M * IQ);
+        VQS_TAP("txt", i, "attn", w.attn, (size_t)M * IQ);
         if (tail)      // this layer's K / V are in w.k / w.v until the next layer's qkv launch
-            QRUN(tail_layer(h, w, i, ln1, ln2, d_seq_len, d_last_row, d_cos, d_sin, B, L, i == 0, st, F, sc.qkv.sigma));
+            VQS_RUN(tail_layer(h, w, i, ln1, ln2, d_seq_len, d_last_row, d_cos, d_sin, B, L, i == 0, st, F, sc.qkv.sigma));
         {
-            GCall g{w.attn, F ? h->t_o_h[i] : h->t_o_w[i], w.delta};
+            GemmCall g{w.attn, F ? h->t_o_h[i] : h->t_o_w[i], w.delta};
             g.M = M; g.N = TH; g.K = IQ; g.lda = IQ; g.ldw = IQ; g.ldc = TH; g.epi = vqs::EPI_BF16;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.qkv.sigma; g.out_scale = sc.dattn.sigma; }
-            QRUN(qgemm(h, g, st, "o_proj"));
+            VQS_RUN(run_gemm(h, g, {}, st, "o_proj"));
         }
-        QTAP("txt", i, "d_attn", w.delta, (size_t)M * TH);
-        QRUN(norm(w.delta, ln2, nullptr, false, sc.dattn.sigma, 1.0f, sc.x1.sigma, false, "post_attention_layernorm"));
-        QRUN(qtap2d(h, "txt", i, "xn1", w.xn, TH, M, XLD, st));
+        VQS_TAP("txt", i, "d_attn", w.delta, (size_t)M * TH);
+        VQS_RUN(norm(w.delta, ln2, nullptr, false, sc.dattn.sigma, 1.0f, sc.x1.sigma, false, "post_attention_layernorm"));
+        VQS_RUN(tap2d(h, "txt", i, "xn1", w.xn, TH, M, XLD, st));
         pend_attn = w.delta; s_pend_attn = sc.dattn.sigma;
         {
-            GCall g{w.xn, F ? h->t_gu_h[i] : h->t_gu_w[i], w.ff};
+            GemmCall g{w.xn, F ? h->t_gu_h[i] : h->t_gu_w[i], w.ff};
             g.M = M; g.N = 2 * h->t_mlp_p; g.K = TH; g.lda = XLD; g.ldw = XLD; g.ldc = h->t_ffld; g.epi = vqs::EPI_GATED; g.gate_act = 1;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x1.sigma; g.out_scale = sc.act.sigma; }
-            QRUN(qgemm(h, g, st, "gate|up"));
+            VQS_RUN(run_gemm(h, g, {}, st, "gate|up"));
         }
-        QTAP("txt", i, "ff", w.ff, (size_t)M * h->t_ffld);
+        VQS_TAP("txt", i, "ff", w.ff, (size_t)M * h->t_ffld);
         {
-            GCall g{w.ff, F ? h->t_down_h[i] : h->t_down_w[i], w.delta2};
+            GemmCall g{w.ff, F ? h->t_down_h[i] : h->t_down_w[i], w.delta2};
             g.M = M; g.N = TH; g.K = h->t_ffld; g.lda = h->t_ffld; g.ldw = h->t_ffld; g.ldc = TH; g.epi = vqs::EPI_BF16;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.act.sigma; g.out_scale = sc.dmlp.sigma; }
-            QRUN(qgemm(h, g, st, "down_proj"));
+            VQS_RUN(run_gemm(h, g, {}, st, "down_proj"));
             pend = w.delta2; s_pend = sc.dmlp.sigma;
         }
-        QTAP("txt", i, "d_mlp", w.delta2, (size_t)M * TH);
+        VQS_TAP("txt", i, "d_mlp", w.delta2, (size_t)M * TH);
     }
-    QW(fin, "model.language_model.norm.weight", TH);
-    QW(head, "lm_head.weight", (int64_t)c.t_vocab * TH);
+    VQS_W(fin, "model.language_model.norm.weight", TH);
+    VQS_W(head, "lm_head.weight", (int64_t)c.t_vocab * TH);
     // the final norm's operand is bf16 in true units either way: lm_head (bf16 weights, fp32 logits) reads it when the tail is off
-    QRUN(norm(pend_attn ? pend_attn : pend, fin, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, 1.0f, true, "final norm"));
-    QTAP("txt", -1, "h_out", w.hidden, (size_t)M * TH);
-    QRUN(qtap2d(h, "txt", -1, "xnf", w.xn, TH, M, XLD, st));
+    VQS_RUN(norm(pend_attn ? pend_attn : pend, fin, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, 1.0f, true, "final norm"));
+    VQS_TAP("txt", -1, "h_out", w.hidden, (size_t)M * TH);
+    VQS_RUN(tap2d(h, "txt", -1, "xnf", w.xn, TH, M, XLD, st));
     if (tail) {
-        QRUN(tail_head(h, w, fin, head, d_logits, B, st));
+        VQS_RUN(tail_head(h, w, fin, head, d_logits, B, st));
         return VQS_OK;
     }
-    QHIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, d_last_row, w.last, B, TH, XLD, TH, st), "last positions");
+    VQS_HIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, d_last_row, w.last, B, TH, XLD, TH, st), "last positions");
     {
-        GCall g{w.last, head, d_logits};
+        GemmCall g{w.last, head, d_logits};
         g.M = B; g.N = c.t_vocab; g.K = TH; g.lda = TH; g.ldw = TH; g.ldc = c.t_vocab; g.epi = vqs::EPI_F32;
-        QRUN(qgemm(h, g, st, "lm_head"));
+        VQS_RUN(run_gemm(h, g, {}, st, "lm_head"));
     }
     return VQS_OK;
 }
@@ -1199,7 +1040,7 @@ DecWs carve_decode(const vqs_qwen_handle* h, char* base, int B) {
         w.part_bytes = b * widest * sizeof(float);
         w.part = cv.take<float>(b * widest);
     }
-    w.total = align_up(cv.off);
+    w.total = cv.total();
     return w;
 }
 
@@ -1212,28 +1053,12 @@ DecWs carve_decode(const vqs_qwen_handle* h, char* base, int B) {
 int decode_linear(vqs_qwen_handle* h, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, bf16_t* out, int ldo, int B,
                   int N, int K, int gated, const DecWs& w, hipStream_t st, const char* what) {
     const int sk = decode_slices(N, K);
-    if ((size_t)sk * B * N * sizeof(float) > w.part_bytes) return qfail(h, VQS_ERR_WORKSPACE, std::string(what) + ": decode scratch too small");
-    vqs::GemmParams p{};
-    p.A = A; p.W = W; p.C = w.part; p.bias = nullptr; p.resid = nullptr;
-    p.M = B; p.N = N; p.K = K / sk; p.lda = lda; p.ldw = ldw; p.ldc = N;
-    p.S = 1; p.H = 0; p.inner = 1;
-    p.batch = sk; p.sA = K / sk; p.sW = K / sk; p.sC = (long long)B * N;
-    if (h->prof) {
-        while (h->ev.size() < h->ev_used + 2) {
-            hipEvent_t e;
-            QHIP(h, hipEventCreate(&e), "hipEventCreate");
-            h->ev.push_back(e);
-        }
-        QHIP(h, hipEventRecord(h->ev[h->ev_used], st), "hipEventRecord");
-    }
-    QHIP(h, vqs::launch_gemm(p, vqs::EPI_F32, 3, st), std::string("gemm ") + what);
-    if (h->prof) {
-        QHIP(h, hipEventRecord(h->ev[h->ev_used + 1], st), "hipEventRecord");
-        h->ev_used += 2;
-        h->prof_flops += 2.0 * (double)B * (double)N * (double)K;
-        h->prof_bytes += 2.0 * ((double)B + (double)N) * (double)K + 4.0 * (double)sk * (double)B * (double)N;
-    }
-    QHIP(h, vqs::launch_reduce_slices_act(w.part, sk, (long long)B * N, B, N, N, bias, gated, out, ldo, st), std::string("reduce ") + what);
+    if ((size_t)sk * B * N * sizeof(float) > w.part_bytes) return fail(h, VQS_ERR_WORKSPACE, std::string(what) + ": decode scratch too small");
+    GemmCall g{A, W, w.part};      // K slices as batch entries, fp32 partials
+    g.M = B; g.N = N; g.K = K / sk; g.lda = lda; g.ldw = ldw; g.ldc = N; g.epi = vqs::EPI_F32;
+    g.batch = sk; g.sA = K / sk; g.sW = K / sk; g.sC = (long long)B * N;
+    VQS_RUN(run_gemm(h, g, {}, st, what));
+    VQS_HIP(h, vqs::launch_reduce_slices_act(w.part, sk, (long long)B * N, B, N, N, bias, gated, out, ldo, st), std::string("reduce ") + what);
     return VQS_OK;
 }
 }  // namespace
@@ -1256,9 +1081,9 @@ int vqs_qwen_prefill(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_
                      const int32_t* d_seq_len, const int32_t* d_last_row, const float* d_cos, const float* d_sin, int32_t B,
                      int32_t L, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv, size_t kv_bytes, int32_t Lmax, void* stream) {
     if (!h) return VQS_ERR_INVALID;
-    if (!d_kv || Lmax < L || kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return qfail(h, VQS_ERR_WORKSPACE, "prefill: KV cache missing or too small");
+    if (!d_kv || Lmax < L || kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return fail(h, VQS_ERR_WORKSPACE, "prefill: KV cache missing or too small");
     if (Lmax > VQS_QWEN_MAX_CACHE_POSITIONS)      // the decode step's one-row attention keeps Lmax fp32 scores in LDS: refuse BEFORE the prefill is spent
-        return qfail(h, VQS_ERR_INVALID, "prefill: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
+        return fail(h, VQS_ERR_INVALID, "prefill: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
     return score_impl(h, d_merged, d_input_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, B, L, d_logits, d_ws, ws_bytes, stream, d_kv,
                       Lmax);
 }
@@ -1271,61 +1096,61 @@ size_t vqs_qwen_decode_workspace_bytes(const vqs_qwen_handle* h, int32_t B) {
 int vqs_qwen_decode(vqs_qwen_handle* h, const int32_t* d_ids, const int32_t* d_len, const float* d_cos, const float* d_sin, int32_t B,
                     int32_t Lmax, void* d_kv, size_t kv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* stream) {
     if (!h) return VQS_ERR_INVALID;
-    if (!h->bound) return qfail(h, VQS_ERR_STATE, "decode: weights not bound");
-    if (!d_ids || !d_len || !d_cos || !d_sin || !d_kv || !d_logits || !d_ws) return qfail(h, VQS_ERR_INVALID, "decode: null argument");
-    if (B <= 0 || Lmax <= 0) return qfail(h, VQS_ERR_INVALID, "decode: need B > 0, Lmax > 0");
-    if (Lmax > VQS_QWEN_MAX_CACHE_POSITIONS) return qfail(h, VQS_ERR_INVALID, "decode: Lmax exceeds " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions");
-    if (kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return qfail(h, VQS_ERR_WORKSPACE, "decode: KV cache too small");
+    if (!h->bound) return fail(h, VQS_ERR_STATE, "decode: weights not bound");
+    if (!d_ids || !d_len || !d_cos || !d_sin || !d_kv || !d_logits || !d_ws) return fail(h, VQS_ERR_INVALID, "decode: null argument");
+    if (B <= 0 || Lmax <= 0) return fail(h, VQS_ERR_INVALID, "decode: need B > 0, Lmax > 0");
+    if (Lmax > VQS_QWEN_MAX_CACHE_POSITIONS) return fail(h, VQS_ERR_INVALID, "decode: Lmax exceeds " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions");
+    if (kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return fail(h, VQS_ERR_WORKSPACE, "decode: KV cache too small");
     const vqs_qwen_config& c = h->c;
     const DecWs w = carve_decode(h, (char*)d_ws, B);
-    if (ws_bytes < w.total) return qfail(h, VQS_ERR_WORKSPACE, "decode: workspace too small");
+    if (ws_bytes < w.total) return fail(h, VQS_ERR_WORKSPACE, "decode: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int TH = c.t_hidden, IQ = h->t_iq, IKV = h->t_ikv, XLD = h->t_xld, QN = IQ + 2 * IKV;
     const float scale = 1.0f / sqrtf((float)h->t_hd);
-    QW(embed, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * TH);
-    QHIP(h, hipMemsetAsync(w.neg1, 0xff, (size_t)B * sizeof(int), st), "no placeholder rows");
-    QHIP(h, vqs::launch_qwen_embed(d_ids, w.neg1, embed, embed, w.hidden, B, TH, c.t_vocab, st), "embed");
-    QHIP(h, hipMemsetAsync(w.ff, 0, (size_t)B * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
-    QTAP("dec", -1, "emb", w.hidden, (size_t)B * TH);
+    VQS_W(embed, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * TH);
+    VQS_HIP(h, hipMemsetAsync(w.neg1, 0xff, (size_t)B * sizeof(int), st), "no placeholder rows");
+    VQS_HIP(h, vqs::launch_qwen_embed(d_ids, w.neg1, embed, embed, w.hidden, B, TH, c.t_vocab, st), "embed");
+    VQS_HIP(h, hipMemsetAsync(w.ff, 0, (size_t)B * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
+    VQS_TAP("dec", -1, "emb", w.hidden, (size_t)B * TH);
     const bf16_t* pend = nullptr;
     const bf16_t* pend_attn = nullptr;
     for (int i = 0; i < c.t_layers; ++i) {
         const std::string p = "model.language_model.layers." + std::to_string(i) + ".";
-        QW(ln1, p + "input_layernorm.weight", TH);
-        QW(ln2, p + "post_attention_layernorm.weight", TH);
+        VQS_W(ln1, p + "input_layernorm.weight", TH);
+        VQS_W(ln2, p + "post_attention_layernorm.weight", TH);
         bf16_t* kc = (bf16_t*)d_kv + (size_t)(2 * i) * kv_slab(h, B, Lmax);
         bf16_t* vc = kc + kv_slab(h, B, Lmax);
-        QHIP(h, vqs::launch_rmsnorm(w.hidden, pend_attn ? pend_attn : pend, ln1, w.xn, B, TH, c.t_eps, st, pend_attn ? pend : nullptr, true, XLD), "input_layernorm");
-        QTAP("dec", i, "h", w.hidden, (size_t)B * TH);
-        QRUN(qtap2d(h, "dec", i, "xn0", w.xn, TH, B, XLD, st));
+        VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, pend_attn ? pend_attn : pend, ln1, w.xn, B, TH, c.t_eps, st, pend_attn ? pend : nullptr, true, XLD), "input_layernorm");
+        VQS_TAP("dec", i, "h", w.hidden, (size_t)B * TH);
+        VQS_RUN(tap2d(h, "dec", i, "xn0", w.xn, TH, B, XLD, st));
         // one position per sample: head-major [B, heads, 1, 128] IS token-major [B, heads * 128]
-        QRUN(decode_linear(h, w.xn, XLD, h->t_qkv_w[i], TH, h->t_qkv_b[i], w.qkv, QN, B, QN, TH, 0, w, st, "decode qkv"));
-        QTAP("dec", i, "qkv", w.qkv, (size_t)B * QN);
-        QHIP(h, vqs::launch_qwen_decode_rope_append(w.qkv, d_cos, d_sin, d_len, w.q, kc, vc, B, c.t_heads, c.t_kv_heads, HDP, h->t_hd / 2, Lmax, st),
+        VQS_RUN(decode_linear(h, w.xn, XLD, h->t_qkv_w[i], TH, h->t_qkv_b[i], w.qkv, QN, B, QN, TH, 0, w, st, "decode qkv"));
+        VQS_TAP("dec", i, "qkv", w.qkv, (size_t)B * QN);
+        VQS_HIP(h, vqs::launch_qwen_decode_rope_append(w.qkv, d_cos, d_sin, d_len, w.q, kc, vc, B, c.t_heads, c.t_kv_heads, HDP, h->t_hd / 2, Lmax, st),
              "decode rope + append");
-        QTAP("dec", i, "q", w.q, (size_t)B * IQ);
-        QHIP(h, vqs::launch_qwen_decode_attn(w.q, kc, vc, d_len, w.attn, B, c.t_heads, c.t_kv_heads, Lmax, scale, st), "decode attention");
-        QTAP("dec", i, "attn", w.attn, (size_t)B * IQ);
-        QRUN(decode_linear(h, w.attn, IQ, h->t_o_w[i], IQ, nullptr, w.delta, TH, B, TH, IQ, 0, w, st, "decode o_proj"));
-        QTAP("dec", i, "d_attn", w.delta, (size_t)B * TH);
-        QHIP(h, vqs::launch_rmsnorm(w.hidden, w.delta, ln2, w.xn, B, TH, c.t_eps, st, nullptr, false, XLD), "post_attention_layernorm");
-        QRUN(qtap2d(h, "dec", i, "xn1", w.xn, TH, B, XLD, st));
+        VQS_TAP("dec", i, "q", w.q, (size_t)B * IQ);
+        VQS_HIP(h, vqs::launch_qwen_decode_attn(w.q, kc, vc, d_len, w.attn, B, c.t_heads, c.t_kv_heads, Lmax, scale, st), "decode attention");
+        VQS_TAP("dec", i, "attn", w.attn, (size_t)B * IQ);
+        VQS_RUN(decode_linear(h, w.attn, IQ, h->t_o_w[i], IQ, nullptr, w.delta, TH, B, TH, IQ, 0, w, st, "decode o_proj"));
+        VQS_TAP("dec", i, "d_attn", w.delta, (size_t)B * TH);
+        VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, w.delta, ln2, w.xn, B, TH, c.t_eps, st, nullptr, false, XLD), "post_attention_layernorm");
+        VQS_RUN(tap2d(h, "dec", i, "xn1", w.xn, TH, B, XLD, st));
         pend_attn = w.delta;
-        QRUN(decode_linear(h, w.xn, XLD, h->t_gu_w[i], XLD, nullptr, w.ff, h->t_ffld, B, 2 * h->t_mlp_p, TH, 1, w, st, "decode gate|up"));
-        QTAP("dec", i, "ff", w.ff, (size_t)B * h->t_ffld);
-        QRUN(decode_linear(h, w.ff, h->t_ffld, h->t_down_w[i], h->t_ffld, nullptr, w.delta2, TH, B, TH, h->t_ffld, 0, w, st, "decode down_proj"));
+        VQS_RUN(decode_linear(h, w.xn, XLD, h->t_gu_w[i], XLD, nullptr, w.ff, h->t_ffld, B, 2 * h->t_mlp_p, TH, 1, w, st, "decode gate|up"));
+        VQS_TAP("dec", i, "ff", w.ff, (size_t)B * h->t_ffld);
+        VQS_RUN(decode_linear(h, w.ff, h->t_ffld, h->t_down_w[i], h->t_ffld, nullptr, w.delta2, TH, B, TH, h->t_ffld, 0, w, st, "decode down_proj"));
         pend = w.delta2;
-        QTAP("dec", i, "d_mlp", w.delta2, (size_t)B * TH);
+        VQS_TAP("dec", i, "d_mlp", w.delta2, (size_t)B * TH);
     }
-    QW(fin, "model.language_model.norm.weight", TH);
-    QW(head, "lm_head.weight", (int64_t)c.t_vocab * TH);
-    QHIP(h, vqs::launch_rmsnorm(w.hidden, pend_attn ? pend_attn : pend, fin, w.xn, B, TH, c.t_eps, st, pend_attn ? pend : nullptr, true, XLD), "final norm");
-    QTAP("dec", -1, "h_out", w.hidden, (size_t)B * TH);
-    QRUN(qtap2d(h, "dec", -1, "xnf", w.xn, TH, B, XLD, st));
+    VQS_W(fin, "model.language_model.norm.weight", TH);
+    VQS_W(head, "lm_head.weight", (int64_t)c.t_vocab * TH);
+    VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, pend_attn ? pend_attn : pend, fin, w.xn, B, TH, c.t_eps, st, pend_attn ? pend : nullptr, true, XLD), "final norm");
+    VQS_TAP("dec", -1, "h_out", w.hidden, (size_t)B * TH);
+    VQS_RUN(tap2d(h, "dec", -1, "xnf", w.xn, TH, B, XLD, st));
     {
-        GCall g{w.xn, head, d_logits};
+        GemmCall g{w.xn, head, d_logits};
         g.M = B; g.N = c.t_vocab; g.K = TH; g.lda = XLD; g.ldw = TH; g.ldc = c.t_vocab; g.epi = vqs::EPI_F32;
-        QRUN(qgemm(h, g, st, "lm_head"));
+        VQS_RUN(run_gemm(h, g, {}, st, "lm_head"));
     }
     return VQS_OK;
 }
@@ -1364,7 +1189,7 @@ SharedWs carve_shared(const vqs_qwen_handle* h, char* base, int R, int Lp, int L
     } else {
         s.key_len = cv.take<int>((size_t)R);
     }
-    s.total = align_up(cv.off);
+    s.total = cv.total();
     return s;
 }
 bool prefix_shape_ok(int U, int Lp) { return U > 0 && Lp >= 32 && (Lp % 32) == 0 && Lp <= VQS_QWEN_MAX_CACHE_POSITIONS; }
@@ -1381,22 +1206,22 @@ int shared_impl(vqs_qwen_handle* h, bool suffix, const void* d_merged, const int
     const int S = suffix ? Ls : Lp;                // rows per sample of this pass
     const int L = suffix ? Lp + Ls : Lp;           // keys per sample of its attention
     const SharedWs sw = carve_shared(h, (char*)d_ws, R, Lp, Ls, suffix);
-    if (ws_bytes < sw.total) return qfail(h, VQS_ERR_WORKSPACE, "shared prefix: workspace too small");
+    if (ws_bytes < sw.total) return fail(h, VQS_ERR_WORKSPACE, "shared prefix: workspace too small");
     const TxtWs& w = sw.w;
     const int TH = c.t_hidden, M = R * S, IKV = h->t_ikv, XLD = h->t_xld;
     const float scale = 1.0f / sqrtf((float)h->t_hd);
     const bool F = h->fp16_active != 0;
-    QW(embed, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * TH);
-    QHIP(h, vqs::launch_qwen_embed(d_ids, d_vis_slot, embed, (const bf16_t*)d_merged, w.hidden, M, TH, c.t_vocab, st, F, F ? 1.0f / h->m_out.sigma : 1.0f), "embed + splice");
-    QHIP(h, hipMemsetAsync(w.ff, 0, (size_t)M * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
+    VQS_W(embed, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * TH);
+    VQS_HIP(h, vqs::launch_qwen_embed(d_ids, d_vis_slot, embed, (const bf16_t*)d_merged, w.hidden, M, TH, c.t_vocab, st, F, F ? 1.0f / h->m_out.sigma : 1.0f), "embed + splice");
+    VQS_HIP(h, hipMemsetAsync(w.ff, 0, (size_t)M * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
     const bool tail = suffix && h->tail_precise != 0 && (c.t_vocab % 4) == 0 && (c.t_hidden % 4) == 0;
-    if (tail) QHIP(h, vqs::launch_gather_rows_f32(w.hidden, d_last_row, w.t_h, R, TH, TH, st), "tail embed rows");
-    if (!suffix) QHIP(h, hipMemsetD32Async((hipDeviceptr_t)sw.key_len, Lp, (size_t)R, st), "prefix key lengths");
+    if (tail) VQS_HIP(h, vqs::launch_gather_rows_f32(w.hidden, d_last_row, w.t_h, R, TH, TH, st), "tail embed rows");
+    if (!suffix) VQS_HIP(h, hipMemsetD32Async((hipDeviceptr_t)sw.key_len, Lp, (size_t)R, st), "prefix key lengths");
     const vqs_qwen_handle::LayerSites one{};
     const bool rope_in_gemm = F && h->rope_fused != 0 && h->t_hd == HDP;
     auto norm = [&](const bf16_t* d, const bf16_t* g, const bf16_t* d2, bool store, float sd1, float sd2, float so, bool out_bf16, const char* what) -> int {
-        if (F) QHIP(h, vqs::launch_rmsnorm_f16s(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD, 1.0f / sd1, 1.0f / sd2, so, out_bf16), what);
-        else QHIP(h, vqs::launch_rmsnorm(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD), what);
+        if (F) VQS_HIP(h, vqs::launch_rmsnorm_f16s(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD, 1.0f / sd1, 1.0f / sd2, so, out_bf16), what);
+        else VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD), what);
         return VQS_OK;
     };
     const bf16_t* pend = nullptr;
@@ -1404,83 +1229,83 @@ int shared_impl(vqs_qwen_handle* h, bool suffix, const void* d_merged, const int
     float s_pend = 1.0f, s_pend_attn = 1.0f;
     for (int i = 0; i < c.t_layers; ++i) {
         const std::string p = "model.language_model.layers." + std::to_string(i) + ".";
-        QW(ln1, p + "input_layernorm.weight", TH);
-        QW(ln2, p + "post_attention_layernorm.weight", TH);
+        VQS_W(ln1, p + "input_layernorm.weight", TH);
+        VQS_W(ln2, p + "post_attention_layernorm.weight", TH);
         const vqs_qwen_handle::LayerSites& sc = F ? h->t_sc[i] : one;
         bf16_t* pk = (bf16_t*)d_pkv + (size_t)(2 * i) * prefix_slab(h, U, Lp);
         bf16_t* pv = pk + prefix_slab(h, U, Lp);
         bf16_t* kout = suffix ? sw.sk : pk;
         bf16_t* vout = suffix ? sw.sv : pv;
-        QRUN(norm(pend_attn ? pend_attn : pend, ln1, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, sc.x0.sigma, false, "input_layernorm"));
+        VQS_RUN(norm(pend_attn ? pend_attn : pend, ln1, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, sc.x0.sigma, false, "input_layernorm"));
         {
-            GCall g{w.xn, F ? h->t_qkv_h[i] : h->t_qkv_w[i], nullptr};
+            GemmCall g{w.xn, F ? h->t_qkv_h[i] : h->t_qkv_w[i], nullptr};
             g.bias = h->t_qkv_b[i];
             g.M = M; g.N = h->t_iq + 2 * IKV; g.K = TH; g.lda = XLD; g.ldw = TH; g.epi = vqs::EPI_HEADS;
             g.S = S; g.H = c.t_heads; g.inner = h->t_iq; g.hd = HDP; g.inner_kv = IKV; g.Hkv = c.t_kv_heads;
             g.heads[0] = w.q; g.heads[1] = kout; g.heads[2] = vout;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x0.sigma; g.out_scale = sc.qkv.sigma; }
             if (rope_in_gemm) { g.rope_cos = d_cos; g.rope_sin = d_sin; }
-            QRUN(qgemm(h, g, st, "qkv"));
+            VQS_RUN(run_gemm(h, g, {}, st, "qkv"));
         }
-        if (!rope_in_gemm) QHIP(h, vqs::launch_rope_qk(w.q, kout, d_cos, d_sin, R, c.t_heads, c.t_kv_heads, S, HDP, h->t_hd / 2, st, F), "rope");
+        if (!rope_in_gemm) VQS_HIP(h, vqs::launch_rope_qk(w.q, kout, d_cos, d_sin, R, c.t_heads, c.t_kv_heads, S, HDP, h->t_hd / 2, st, F), "rope");
         if (!suffix && i == c.t_layers - 1) break;     // the last layer's K / V are all the suffix pass reads of the prefix
         const float a_scale = scale / (sc.qkv.sigma * sc.qkv.sigma);
         if (suffix) {
-            QHIP(h, vqs::launch_qwen_kv_assemble(pk, pv, sw.sk, sw.sv, d_media_idx, w.k, w.v, R, U, c.t_kv_heads, Lp, Ls, st), "assemble K / V slabs");
+            VQS_HIP(h, vqs::launch_qwen_kv_assemble(pk, pv, sw.sk, sw.sv, d_media_idx, w.k, w.v, R, U, c.t_kv_heads, Lp, Ls, st), "assemble K / V slabs");
             if (d_kv) {   // as score_impl: rows [b, head, 0 .. L) of the cache slabs, bf16 in true units
                 bf16_t* kc = (bf16_t*)d_kv + (size_t)(2 * i) * kv_slab(h, R, Lmax);
                 bf16_t* vc = kc + kv_slab(h, R, Lmax);
                 const size_t wb = (size_t)L * HDP * sizeof(bf16_t), pb = (size_t)Lmax * HDP * sizeof(bf16_t), nr = (size_t)R * c.t_kv_heads;
                 if (F) {
-                    if (nr > 65535) return qfail(h, VQS_ERR_INVALID, "prefill: B * kv_heads exceeds 65535");
-                    QHIP(h, vqs::launch_f16_to_bf16_rows(w.k, kc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep K");
-                    QHIP(h, vqs::launch_f16_to_bf16_rows(w.v, vc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep V");
+                    if (nr > 65535) return fail(h, VQS_ERR_INVALID, "prefill: B * kv_heads exceeds 65535");
+                    VQS_HIP(h, vqs::launch_f16_to_bf16_rows(w.k, kc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep K");
+                    VQS_HIP(h, vqs::launch_f16_to_bf16_rows(w.v, vc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep V");
                 } else {
-                    QHIP(h, hipMemcpy2DAsync(kc, pb, w.k, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep K");
-                    QHIP(h, hipMemcpy2DAsync(vc, pb, w.v, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep V");
+                    VQS_HIP(h, hipMemcpy2DAsync(kc, pb, w.k, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep K");
+                    VQS_HIP(h, hipMemcpy2DAsync(vc, pb, w.v, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep V");
                 }
             }
             vqs::AttnSuffixParams a{w.q, w.k, w.v, w.attn, d_seq_len, R, c.t_heads, c.t_kv_heads, L, Ls, Lp, a_scale};
             a.f16 = F ? 1 : 0;
-            QHIP(h, vqs::launch_attention_suffix(a, st), "suffix attention");
+            VQS_HIP(h, vqs::launch_attention_suffix(a, st), "suffix attention");
         } else {
             vqs::AttnParams a{w.q, pk, pv, w.attn, nullptr, sw.key_len, R, c.t_heads, Lp, a_scale};
             a.hd = HDP; a.Hkv = c.t_kv_heads; a.causal = 1; a.f16 = F ? 1 : 0;
-            QHIP(h, vqs::launch_attention(a, st), "prefix attention");
+            VQS_HIP(h, vqs::launch_attention(a, st), "prefix attention");
         }
-        if (tail) QRUN(tail_layer(h, w, i, ln1, ln2, d_seq_len, d_last_row, d_cos, d_sin, R, L, i == 0, st, F, sc.qkv.sigma));
+        if (tail) VQS_RUN(tail_layer(h, w, i, ln1, ln2, d_seq_len, d_last_row, d_cos, d_sin, R, L, i == 0, st, F, sc.qkv.sigma));
         {
-            GCall g{w.attn, F ? h->t_o_h[i] : h->t_o_w[i], w.delta};
+            GemmCall g{w.attn, F ? h->t_o_h[i] : h->t_o_w[i], w.delta};
             g.M = M; g.N = TH; g.K = h->t_iq; g.lda = h->t_iq; g.ldw = h->t_iq; g.ldc = TH; g.epi = vqs::EPI_BF16;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.qkv.sigma; g.out_scale = sc.dattn.sigma; }
-            QRUN(qgemm(h, g, st, "o_proj"));
+            VQS_RUN(run_gemm(h, g, {}, st, "o_proj"));
         }
-        QRUN(norm(w.delta, ln2, nullptr, false, sc.dattn.sigma, 1.0f, sc.x1.sigma, false, "post_attention_layernorm"));
+        VQS_RUN(norm(w.delta, ln2, nullptr, false, sc.dattn.sigma, 1.0f, sc.x1.sigma, false, "post_attention_layernorm"));
         pend_attn = w.delta; s_pend_attn = sc.dattn.sigma;
         {
-            GCall g{w.xn, F ? h->t_gu_h[i] : h->t_gu_w[i], w.ff};
+            GemmCall g{w.xn, F ? h->t_gu_h[i] : h->t_gu_w[i], w.ff};
             g.M = M; g.N = 2 * h->t_mlp_p; g.K = TH; g.lda = XLD; g.ldw = XLD; g.ldc = h->t_ffld; g.epi = vqs::EPI_GATED; g.gate_act = 1;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x1.sigma; g.out_scale = sc.act.sigma; }
-            QRUN(qgemm(h, g, st, "gate|up"));
+            VQS_RUN(run_gemm(h, g, {}, st, "gate|up"));
         }
         {
-            GCall g{w.ff, F ? h->t_down_h[i] : h->t_down_w[i], w.delta2};
+            GemmCall g{w.ff, F ? h->t_down_h[i] : h->t_down_w[i], w.delta2};
             g.M = M; g.N = TH; g.K = h->t_ffld; g.lda = h->t_ffld; g.ldw = h->t_ffld; g.ldc = TH; g.epi = vqs::EPI_BF16;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.act.sigma; g.out_scale = sc.dmlp.sigma; }
-            QRUN(qgemm(h, g, st, "down_proj"));
+            VQS_RUN(run_gemm(h, g, {}, st, "down_proj"));
             pend = w.delta2; s_pend = sc.dmlp.sigma;
         }
     }
     if (!suffix) return VQS_OK;
-    QW(fin, "model.language_model.norm.weight", TH);
-    QW(head, "lm_head.weight", (int64_t)c.t_vocab * TH);
-    QRUN(norm(pend_attn ? pend_attn : pend, fin, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, 1.0f, true, "final norm"));
+    VQS_W(fin, "model.language_model.norm.weight", TH);
+    VQS_W(head, "lm_head.weight", (int64_t)c.t_vocab * TH);
+    VQS_RUN(norm(pend_attn ? pend_attn : pend, fin, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, 1.0f, true, "final norm"));
     if (tail) return tail_head(h, w, fin, head, d_logits, R, st);
-    QHIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, d_last_row, w.last, R, TH, XLD, TH, st), "last positions");
+    VQS_HIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, d_last_row, w.last, R, TH, XLD, TH, st), "last positions");
     {
-        GCall g{w.last, head, d_logits};
+        GemmCall g{w.last, head, d_logits};
         g.M = R; g.N = c.t_vocab; g.K = TH; g.lda = TH; g.ldw = TH; g.ldc = c.t_vocab; g.epi = vqs::EPI_F32;
-        QRUN(qgemm(h, g, st, "lm_head"));
+        VQS_RUN(run_gemm(h, g, {}, st, "lm_head"));
     }
     return VQS_OK;
 }
@@ -1492,16 +1317,16 @@ int suffix_entry(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids,
     if (!h) return VQS_ERR_INVALID;
     // sizes first: an invalid shape is refused whatever else is wrong with the call
     if (!suffix_shape_ok(B, Lp, Ls) || !prefix_shape_ok(U, Lp))
-        return qfail(h, VQS_ERR_INVALID, "score_suffix: need B, U > 0, Lp a multiple of 32 (>= 32), Ls >= 8, Lp + Ls <= " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS));
+        return fail(h, VQS_ERR_INVALID, "score_suffix: need B, U > 0, Lp a multiple of 32 (>= 32), Ls >= 8, Lp + Ls <= " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS));
     if (cached && Lmax > VQS_QWEN_MAX_CACHE_POSITIONS)
-        return qfail(h, VQS_ERR_INVALID, "prefill_suffix: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
-    if (!h->bound) return qfail(h, VQS_ERR_STATE, "score_suffix: weights not bound");
+        return fail(h, VQS_ERR_INVALID, "prefill_suffix: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
+    if (!h->bound) return fail(h, VQS_ERR_STATE, "score_suffix: weights not bound");
     if (!d_merged || !d_ids || !d_vis_slot || !d_seq_len || !d_last_row || !d_cos || !d_sin || !d_media_idx || !d_pkv || !d_logits || !d_ws)
-        return qfail(h, VQS_ERR_INVALID, "score_suffix: null argument");
-    if (pkv_bytes < vqs_qwen_prefix_kv_bytes(h, U, Lp)) return qfail(h, VQS_ERR_WORKSPACE, "score_suffix: prefix store too small");
+        return fail(h, VQS_ERR_INVALID, "score_suffix: null argument");
+    if (pkv_bytes < vqs_qwen_prefix_kv_bytes(h, U, Lp)) return fail(h, VQS_ERR_WORKSPACE, "score_suffix: prefix store too small");
     if (cached) {
-        if (!d_kv || Lmax < Lp + Ls || kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return qfail(h, VQS_ERR_WORKSPACE, "prefill_suffix: KV cache missing or too small");
-        if (h->fp16_active && (int64_t)B * h->c.t_kv_heads > 65535) return qfail(h, VQS_ERR_INVALID, "prefill_suffix: B * kv_heads exceeds 65535");
+        if (!d_kv || Lmax < Lp + Ls || kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return fail(h, VQS_ERR_WORKSPACE, "prefill_suffix: KV cache missing or too small");
+        if (h->fp16_active && (int64_t)B * h->c.t_kv_heads > 65535) return fail(h, VQS_ERR_INVALID, "prefill_suffix: B * kv_heads exceeds 65535");
     }
     return shared_impl(h, true, d_merged, d_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, d_media_idx, B, U, Lp, Ls, d_pkv, pkv_bytes, d_logits,
                        d_ws, ws_bytes, cached ? d_kv : nullptr, Lmax, (hipStream_t)stream);
@@ -1529,10 +1354,10 @@ int vqs_qwen_prefix(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_i
                     int32_t U, int32_t Lp, void* d_pkv, size_t pkv_bytes, void* d_ws, size_t ws_bytes, void* stream) {
     if (!h) return VQS_ERR_INVALID;
     if (!prefix_shape_ok(U, Lp))       // sizes first, as vqs_qwen_score_suffix
-        return qfail(h, VQS_ERR_INVALID, "prefix: need U > 0 and Lp a multiple of 32 in [32, " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + "]");
-    if (!h->bound) return qfail(h, VQS_ERR_STATE, "prefix: weights not bound");
-    if (!d_merged || !d_ids || !d_vis_slot || !d_cos || !d_sin || !d_pkv || !d_ws) return qfail(h, VQS_ERR_INVALID, "prefix: null argument");
-    if (pkv_bytes < vqs_qwen_prefix_kv_bytes(h, U, Lp)) return qfail(h, VQS_ERR_WORKSPACE, "prefix: prefix store too small");
+        return fail(h, VQS_ERR_INVALID, "prefix: need U > 0 and Lp a multiple of 32 in [32, " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + "]");
+    if (!h->bound) return fail(h, VQS_ERR_STATE, "prefix: weights not bound");
+    if (!d_merged || !d_ids || !d_vis_slot || !d_cos || !d_sin || !d_pkv || !d_ws) return fail(h, VQS_ERR_INVALID, "prefix: null argument");
+    if (pkv_bytes < vqs_qwen_prefix_kv_bytes(h, U, Lp)) return fail(h, VQS_ERR_WORKSPACE, "prefix: prefix store too small");
     return shared_impl(h, false, d_merged, d_ids, d_vis_slot, nullptr, nullptr, d_cos, d_sin, nullptr, U, U, Lp, 0, d_pkv, pkv_bytes, nullptr, d_ws,
                        ws_bytes, nullptr, 0, (hipStream_t)stream);
 }

@@ -3,6 +3,7 @@
 #include "vqs.h"
 #include "vqs_debug.h"
 #include "vqs_qwen.h"
+#include "vqs_clip.h"
 #include <cassert>
 #include <cstdio>
 #include <cstring>
@@ -116,6 +117,51 @@ int main() {
         vqs_qwen_destroy(qh);
         q.t_heads = 27;        // hidden not divisible by heads
         assert(vqs_qwen_create(&q, &qh) != 0);
+    }
+    {   // CLIPScore row (ViT-L/14-336): sizes, options, refused configurations and the passes that must fail cleanly before any device access
+        vqs_clip_config k;
+        memset(&k, 0, sizeof k);
+        k.vis_hidden = 1024; k.vis_layers = 24; k.vis_heads = 16; k.vis_mlp = 4096; k.vis_patch = 14; k.vis_image = 336; k.vis_eps = 1e-5f;
+        k.txt_hidden = 768; k.txt_layers = 12; k.txt_heads = 12; k.txt_mlp = 3072; k.txt_vocab = 49408; k.txt_context = 77; k.txt_eps = 1e-5f;
+        k.embed_dim = 768;
+        vqs_clip_handle* kh = nullptr;
+        assert(vqs_clip_create(&k, &kh) == 0 && kh);
+        assert(vqs_clip_packed_bytes(kh) > 0 && vqs_clip_packed_bytes(nullptr) == 0);
+        assert(vqs_clip_image_workspace_bytes(kh, 256) > 0 && vqs_clip_image_workspace_bytes(kh, 0) == 0);
+        assert(vqs_clip_text_workspace_bytes(kh, 256, 77) > 0 && vqs_clip_text_workspace_bytes(kh, 4, 8) > 0);
+        assert(vqs_clip_text_workspace_bytes(kh, 4, 78) == 0 && vqs_clip_text_workspace_bytes(kh, 4, 7) == 0 && vqs_clip_text_workspace_bytes(kh, 0, 77) == 0);
+        {
+            int32_t v = -1;
+            assert(vqs_clip_get_option(kh, "fp16", &v) == 0 && v == 1 && vqs_clip_get_option(kh, "norm_defer", &v) == 0 && v == 1);
+            assert(vqs_clip_set_option(kh, "fp16", 0) == 0 && vqs_clip_get_option(kh, "fp16", &v) == 0 && v == 0 && vqs_clip_set_option(kh, "fp16", 1) == 0);
+            assert(vqs_clip_set_option(kh, "fp16", 2) != 0 && strlen(vqs_clip_last_error(kh)) > 0);
+            assert(vqs_clip_set_option(kh, "vit_fp16", 1) != 0 && vqs_clip_set_option(kh, nullptr, 1) != 0 && vqs_clip_set_option(nullptr, "fp16", 1) != 0);
+            assert(vqs_clip_get_option(kh, "nonsense", &v) != 0 && vqs_clip_get_option(kh, "fp16", nullptr) != 0 && vqs_clip_get_option(nullptr, "fp16", &v) != 0);
+        }
+        float emb = 0.f;
+        assert(vqs_clip_encode_images(kh, &dummy, 1, &emb, &dummy, (size_t)1 << 40, nullptr) == VQS_ERR_STATE);      // weights not bound
+        assert(strstr(vqs_clip_last_error(kh), "not bound") != nullptr);
+        assert(vqs_clip_encode_texts(kh, &dummy, &dummy, 1, 77, &emb, &dummy, (size_t)1 << 40, nullptr) == VQS_ERR_STATE);
+        assert(strstr(vqs_clip_last_error(kh), "encode_texts") != nullptr && strstr(vqs_clip_last_error(kh), "not bound") != nullptr);
+        assert(vqs_clip_encode_images(nullptr, &dummy, 1, &emb, &dummy, 16, nullptr) == VQS_ERR_INVALID);
+        assert(vqs_clip_bind_weights(kh, nullptr, 0, nullptr, 0, nullptr) == VQS_ERR_INVALID && strlen(vqs_clip_last_error(kh)) > 0);
+        vqs_clip_destroy(kh);
+        // refused configurations: the handle comes back (for its message), sizes as 0, and binds to nothing
+        struct { int32_t vqs_clip_config::*field; int32_t value; const char* word; } bad_cfg[] = {
+            {&vqs_clip_config::txt_heads, 16, "text head dim"}, {&vqs_clip_config::vis_heads, 8, "vision head dim"},
+            {&vqs_clip_config::txt_context, 129, "txt_context"}, {&vqs_clip_config::vis_image, 330, "multiple of the patch"},
+            {&vqs_clip_config::embed_dim, 770, "embed_dim"}, {&vqs_clip_config::txt_layers, 0, "layer counts"}};
+        for (const auto& b : bad_cfg) {
+            vqs_clip_config kb = k;
+            kb.*(b.field) = b.value;
+            vqs_clip_handle* hb2 = nullptr;
+            assert(vqs_clip_create(&kb, &hb2) == VQS_ERR_INVALID && hb2 && strstr(vqs_clip_last_error(hb2), b.word) != nullptr);
+            assert(vqs_clip_packed_bytes(hb2) == 0 && vqs_clip_image_workspace_bytes(hb2, 1) == 0 && vqs_clip_text_workspace_bytes(hb2, 1, 77) == 0);
+            assert(vqs_clip_bind_weights(hb2, nullptr, 0, nullptr, 0, nullptr) == VQS_ERR_STATE);
+            vqs_clip_destroy(hb2);
+        }
+        assert(vqs_clip_create(nullptr, &kh) != 0 && strcmp(vqs_clip_last_error(nullptr), "null handle") == 0);
+        vqs_clip_destroy(nullptr);
     }
     printf("host ABI exercise under ASan/UBSan: ok\n");
     return 0;

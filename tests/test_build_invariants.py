@@ -224,7 +224,8 @@ def test_shipped_library_has_no_lab_code_and_reads_no_environment():
         pytest.skip("library not built")
     undefined = subprocess.check_output(["nm", "-D", "--undefined-only", lib], text=True)
     assert "getenv" not in undefined, "the shipped library must not read environment variables"
-    for src in ("gemm.hip", "attn.hip", "elementwise.hip", "vqs_api.cpp", "vqs_qwen.cpp"):
+    for src in ("gemm.hip", "attn.hip", "elementwise.hip", "qwen_decode.hip", "clip.hip", "vqs_api.cpp", "vqs_qwen.cpp", "vqs_clip.cpp",
+                "vqs_blocks.h", "vqs_host.h"):
         text = open(os.path.join(CSRC, src)).read()
         assert "getenv" not in text and "VQS_LAB" not in text, src + ": environment switch / lab flavour is back"
         assert "VQS_ABLATE" not in text and "VQS_ATTN_ABLATE" not in text, src + ": ablation scaffolding is back"

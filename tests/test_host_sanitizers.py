@@ -1,4 +1,4 @@
-"""Host code of the C ABI (vqs_api.cpp, vqs_qwen.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer (no GPU
+"""Host code of the C ABI (vqs_api.cpp, vqs_qwen.cpp, vqs_clip.cpp and the layer they share, vqs_host.h) under AddressSanitizer + UndefinedBehaviorSanitizer (no GPU
 needed): a C++ driver (tests/cabi/host_abi_exercise.cpp) walks everything that runs before the first device access --
 handle creation and validation, workspace / packed-buffer sizing, the option setter, tap registration, named workspace
 offsets, the argument checks of the pass entry points, the integer helpers -- linked against the sanitised host objects
@@ -18,7 +18,7 @@ pytestmark = pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(CL
 
 
 def test_host_abi_under_asan_and_ubsan():
-    dev_objs = [os.path.join(OBJ, f) for f in ("gemm.hip.o", "attn.hip.o", "elementwise.hip.o", "qwen_decode.hip.o")]
+    dev_objs = [os.path.join(OBJ, f) for f in ("gemm.hip.o", "attn.hip.o", "elementwise.hip.o", "qwen_decode.hip.o", "clip.hip.o")]
     if not all(os.path.exists(o) for o in dev_objs):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "t2v_metrics_amd", "csrc"), "-j4"], stdout=subprocess.DEVNULL)
     out = os.path.join(ROOT, "build", "asan")
@@ -27,14 +27,15 @@ def test_host_abi_under_asan_and_ubsan():
     san = ["-fsanitize=address,undefined", "-fno-gpu-sanitize", "-Wno-unused-command-line-argument", "-fno-omit-frame-pointer", "-O1", "-g",
            "-std=c++17"]
     csrc = os.path.join(ROOT, "t2v_metrics_amd", "csrc")
-    for src in ("vqs_api.cpp", "vqs_qwen.cpp"):
+    host = ("vqs_api.cpp", "vqs_qwen.cpp", "vqs_clip.cpp")
+    for src in host:
         subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-fPIC", *san, "-c", os.path.join(csrc, src), "-o",
                                os.path.join(out, src + ".o")], stderr=subprocess.DEVNULL)
     subprocess.check_call([CLANG, *san, "-I" + os.path.join(ROOT, "include"), "-c",
                            os.path.join(ROOT, "tests", "cabi", "host_abi_exercise.cpp"), "-o", os.path.join(out, "driver.o")])
     exe = os.path.join(out, "host_abi_exercise")
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-fsanitize=address,undefined", "-fno-gpu-sanitize", os.path.join(out, "driver.o"),
-                           os.path.join(out, "vqs_api.cpp.o"), os.path.join(out, "vqs_qwen.cpp.o"), *dev_objs, "-o", exe],
+                           *[os.path.join(out, src + ".o") for src in host], *dev_objs, "-o", exe],
                           stderr=subprocess.DEVNULL)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     p = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
