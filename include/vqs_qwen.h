@@ -150,6 +150,8 @@ int vqs_qwen_prefill_suffix(vqs_qwen_handle* h, const void* d_merged, const int3
  * vis.{h_out,xnm,mid,merged_w}; txt.emb, txt.<i>.{h,xn0,q0,k0,q,k,v,attn,d_attn,xn1,ff,d_mlp}, txt.{h_out,xnf}; of vqs_qwen_decode:
  * dec.emb, dec.<i>.{h,xn0,qkv,q,attn,d_attn,xn1,ff,d_mlp}, dec.{h_out,xnf} -- tensors in the ENGINE's
  * layouts (padded windowed rows, 128-lane heads, q0 / k0 before and q / k after the rotary embedding, padded ff width).  name == NULL clears every tap.
+ * The txt taps fire in every language-model pass, vqs_qwen_prefix and the two suffix calls included, with that pass's own tensors: its rows
+ * (U x Lp or B x Ls) in the row-wise taps, and in txt.<i>.{k,v} the slabs its attention reads (U x kv_heads x Lp x 128, or B x kv_heads x (Lp + Ls) x 128).
  * tests/test_gpu_qwen.py checks every launch of a pass against the rounding-matched oracle through it. */
 int vqs_qwen_debug_tap(vqs_qwen_handle* h, const char* name, void* d_dst, size_t bytes);
 

@@ -399,7 +399,7 @@ VisWs carve_vision(const vqs_qwen_handle* h, char* base, int N, int Np) {
     return w;
 }
 
-// K slices of a decode-step linear (decode_linear below): the fewest slices (a divisor of K / 64, <= 16) that put >= 192
+// K slices of a decode-step or precise-tail linear (sliced_linear below): the fewest slices (a divisor of K / 64, <= 16) that put >= 192
 // (slice, 128-column) items on the chip -- a function of the weight's shape only.  carve_decode sizes the partial buffer with it.
 int decode_slices(int N, int K) {
     const int nblk = (N + 127) / 128, nsl = K / 64;
@@ -411,6 +411,19 @@ int decode_slices(int N, int K) {
             if (nblk * s2 >= 192) break;
         }
     return best;
+}
+// Widest partial set of a language-model layer's four linears (and of lm_head, for the precise tail): slices(N, K) x N fp32 per row, by
+// the SAME rule sliced_linear launches with (a hand-written bound missed gate|up with two slices -- Qwen2.5-VL-3B's
+// 2048 / 11008 -- and every decode step failed)
+size_t widest_partials(const vqs_qwen_handle* h, bool lm_head) {
+    const vqs_qwen_config& c = h->c;
+    const int QN = h->t_iq + 2 * h->t_ikv;
+    size_t widest = (size_t)decode_slices(QN, c.t_hidden) * QN;                                       // qkv
+    widest = std::max(widest, (size_t)decode_slices(c.t_hidden, h->t_iq) * c.t_hidden);               // o_proj
+    widest = std::max(widest, (size_t)decode_slices(2 * h->t_mlp_p, c.t_hidden) * 2 * h->t_mlp_p);    // gate|up
+    widest = std::max(widest, (size_t)decode_slices(c.t_hidden, h->t_ffld) * c.t_hidden);             // down_proj
+    if (lm_head) widest = std::max(widest, (size_t)decode_slices(c.t_vocab, c.t_hidden) * c.t_vocab);
+    return widest;
 }
 
 static constexpr int TAIL_ROWS = 64;      // samples per chunk of the precise tail: 2 x 64 stacked rows = the stream GEMM form's 128-row limit
@@ -449,11 +462,7 @@ TxtWs carve_text(const vqs_qwen_handle* h, char* base, int B, int L) {
         w.t_xn = cv.take<bf16_t>(2 * Bc * c.t_hidden);
         w.t_attn = cv.take<bf16_t>(2 * Bc * h->t_iq);
         w.t_ff = cv.take<bf16_t>(2 * Bc * h->t_ffld);
-        size_t widest = (size_t)decode_slices((int)QN, c.t_hidden) * QN;
-        widest = std::max(widest, (size_t)decode_slices(c.t_hidden, h->t_iq) * c.t_hidden);
-        widest = std::max(widest, (size_t)decode_slices(2 * h->t_mlp_p, c.t_hidden) * 2 * h->t_mlp_p);
-        widest = std::max(widest, (size_t)decode_slices(c.t_hidden, h->t_ffld) * c.t_hidden);
-        widest = std::max(widest, (size_t)decode_slices(c.t_vocab, c.t_hidden) * c.t_vocab);
+        const size_t widest = widest_partials(h, true);
         w.t_part_bytes = 2 * Bc * widest * sizeof(float);
         w.t_part = cv.take<float>(2 * Bc * widest);
     }
@@ -825,16 +834,24 @@ inline size_t kv_slab(const vqs_qwen_handle* h, int B, int Lmax) { return (size_
 // (HF Qwen2_5_VLDecoderLayer, modeling_qwen2_5_vl.py:720-787), evaluated closer to fp32 -- like the CLIP-FlanT5 row's precise decoder.
 // Cost: the language model's weights streamed once more per chunk of 64 samples (~1 % of the 7B pass at B = 64).
 // ---------------------------------------------------------------------------------------------------------------------------------
-// One nn.Linear of the tail: A2 = split-bf16 [2][rows][lda] (planes rows * lda apart) as 2 * rows stacked rows, K slices as batch
-// entries (decode_slices: the decode step's rule), fp32 partials, then launch_sum_planes adds planes and slices (+ bias / SiLU gate).
+// One nn.Linear over K slices as batch entries (decode_slices: a function of the weight's shape only) into the fp32 partials
+// part[slices][rows][N]; *slices = their number.  The caller's reducer adds the slices and applies the epilogue.
+int sliced_linear(vqs_qwen_handle* h, const bf16_t* A, int lda, const bf16_t* W, int ldw, int rows, int N, int K, float* part, size_t part_bytes,
+                  const char* owner, hipStream_t st, const char* what, int* slices) {
+    const int sk = *slices = decode_slices(N, K);
+    if ((size_t)sk * rows * N * sizeof(float) > part_bytes) return fail(h, VQS_ERR_WORKSPACE, std::string(what) + ": " + owner + " scratch too small");
+    GemmCall g{A, W, part};
+    g.M = rows; g.N = N; g.K = K / sk; g.lda = lda; g.ldw = ldw; g.ldc = N; g.epi = vqs::EPI_F32;
+    g.batch = sk; g.sA = K / sk; g.sW = K / sk; g.sC = (long long)rows * N;
+    return run_gemm(h, g, {}, st, what);
+}
+
+// One nn.Linear of the tail: A2 = split-bf16 [2][rows][lda] (planes rows * lda apart) as 2 * rows stacked rows of sliced_linear, then
+// launch_sum_planes adds planes and slices (+ bias / SiLU gate).
 int tail_linear(vqs_qwen_handle* h, const bf16_t* A2, int lda, const bf16_t* W, int ldw, const bf16_t* bias, int rows, int N, int K, int mode,
                 void* out, int ld_out, long long out_plane, const TxtWs& w, hipStream_t st, const char* what) {
-    const int sk = decode_slices(N, K);
-    if ((size_t)sk * 2 * rows * N * sizeof(float) > w.t_part_bytes) return fail(h, VQS_ERR_WORKSPACE, std::string(what) + ": tail scratch too small");
-    GemmCall g{A2, W, w.t_part};      // K slices as batch entries, fp32 partials
-    g.M = 2 * rows; g.N = N; g.K = K / sk; g.lda = lda; g.ldw = ldw; g.ldc = N; g.epi = vqs::EPI_F32;
-    g.batch = sk; g.sA = K / sk; g.sW = K / sk; g.sC = (long long)2 * rows * N;
-    VQS_RUN(run_gemm(h, g, {}, st, what));
+    int sk;
+    VQS_RUN(sliced_linear(h, A2, lda, W, ldw, 2 * rows, N, K, w.t_part, w.t_part_bytes, "tail", st, what, &sk));
     VQS_HIP(h, vqs::launch_sum_planes(w.t_part, sk, (long long)2 * rows * N, rows, N, N, mode, out, ld_out, out_plane, st, bias,
                                    mode == vqs::SUM_GATED_SPLIT ? 1 : 0), std::string("sum ") + what);
     return VQS_OK;
@@ -880,38 +897,147 @@ int tail_head(vqs_qwen_handle* h, const TxtWs& w, const bf16_t* fin, const bf16_
     return VQS_OK;
 }
 
-// vqs_qwen_score / vqs_qwen_prefill: d_kv != nullptr also keeps every layer's K and V
-int score_impl(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_input_ids, const int32_t* d_vis_slot,
-               const int32_t* d_seq_len, const int32_t* d_last_row, const float* d_cos, const float* d_sin, int32_t B,
-               int32_t L, float* d_logits, void* d_ws, size_t ws_bytes, void* stream, void* d_kv, int32_t Lmax) {
-    if (!h) return VQS_ERR_INVALID;
-    if (!h->bound) return fail(h, VQS_ERR_STATE, "score: weights not bound");
-    if (!d_merged || !d_input_ids || !d_vis_slot || !d_seq_len || !d_last_row || !d_cos || !d_sin || !d_logits || !d_ws)
-        return fail(h, VQS_ERR_INVALID, "score: null argument");
-    if (B <= 0 || L <= 0) return fail(h, VQS_ERR_INVALID, "score: need B > 0, L > 0");
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Shared prompt prefix (include/vqs_qwen.h vqs_qwen_prefix / vqs_qwen_score_suffix / vqs_qwen_prefill_suffix).  The first Lp rows of
+// every prompt about one medium are the same tokens at the same positions, and the language model is causal: their K / V in every layer
+// do not depend on the question.  The PREFIX pass runs text_pass's layer sequence over U prefixes and leaves each layer's K (rotated) and
+// V in the prefix store, in the tensors the attention reads (bf16, or fp16 behind the layer's q|k|v scale).  The SUFFIX pass runs the
+// same sequence over the suffix rows only; per layer, launch_qwen_kv_assemble builds the [B, Hkv, Lp + Ls, 128] slabs the FULL pass has in
+// w.k / w.v (prefix rows from the store, suffix rows from the q|k|v launch), and the precise tail, the cache copy and the decode step read
+// them unchanged.  Every launch is row-independent (GEMM forms are a function of the weight's shape, never of M; norms, embedding and rope
+// are per row) except attention, whose rows couple through the wave-uniform deferred rescale: Lp is a multiple of 32 so that the prefix
+// pass (attn_fwd_hd_kernel over Lp rows) and the suffix pass (attn_suffix_hd_kernel over rows [Lp, L)) hold the same 32-row waves as
+// the full kernel over L rows.  Result: bitwise the logits and cache of vqs_qwen_score / vqs_qwen_prefill over the whole prompts.
+// ---------------------------------------------------------------------------------------------------------------------------------
+inline size_t prefix_slab(const vqs_qwen_handle* h, int U, int Lp) { return (size_t)U * h->c.t_kv_heads * (size_t)Lp * HDP; }
+
+struct SharedWs {
+    TxtWs w;
+    bf16_t *sk = nullptr, *sv = nullptr;   // suffix pass: the suffix rows' own K / V [B, Hkv, Ls, 128]
+    int* key_len = nullptr;                // prefix pass: Lp per prefix
+    size_t total = 0;
+};
+SharedWs carve_shared(const vqs_qwen_handle* h, char* base, int R, int Lp, int Ls, bool suffix) {
+    SharedWs s;
+    s.w = carve_text(h, base, R, suffix ? Lp + Ls : Lp);
+    Carver cv{base};
+    cv.off = s.w.total;
+    if (suffix) {
+        s.sk = cv.take<bf16_t>((size_t)R * Ls * h->t_ikv);
+        s.sv = cv.take<bf16_t>((size_t)R * Ls * h->t_ikv);
+    } else {
+        s.key_len = cv.take<int>((size_t)R);
+    }
+    s.total = cv.total();
+    return s;
+}
+bool prefix_shape_ok(int U, int Lp) { return U > 0 && Lp >= 32 && (Lp % 32) == 0 && Lp <= VQS_QWEN_MAX_CACHE_POSITIONS; }
+bool suffix_shape_ok(int B, int Lp, int Ls) {
+    return B > 0 && Lp >= 32 && (Lp % 32) == 0 && Ls >= 8 && (int64_t)Lp + Ls <= VQS_QWEN_MAX_CACHE_POSITIONS;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The language-model pass: the ONE launch sequence behind vqs_qwen_score / vqs_qwen_prefill (FULL: R whole prompts), vqs_qwen_prefix
+// (PREFIX: R = U prompt prefixes of Lp rows; ends with the last layer's K / V in the prefix store) and vqs_qwen_score_suffix /
+// vqs_qwen_prefill_suffix (SUFFIX: R suffixes of Ls rows behind the prefixes of media d_media_idx).  The modes differ in the few named
+// steps at the head of text_pass and nowhere else, so the shared-prefix results equal the unshared ones by construction.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct TextPass {
+    enum Mode { FULL, PREFIX, SUFFIX } mode;
+    int R, S, L;      // samples, rows per sample this pass computes, keys per sample its attention sees
+    // the mode's extras
+    int U = 0, Lp = 0, Ls = 0;
+    const int32_t* d_media_idx = nullptr;
+    const void* d_pkv = nullptr;      // prefix store: written by PREFIX, read by SUFFIX
+    void* d_kv = nullptr;             // FULL / SUFFIX: != nullptr also keeps every layer's K and V in the decode cache (pitch Lmax positions)
+    int Lmax = 0;
+    const int32_t *d_seq_len = nullptr, *d_last_row = nullptr;
+    float* d_logits = nullptr;
+};
+SharedWs carve_pass(const vqs_qwen_handle* h, char* base, const TextPass& t) {
+    if (t.mode != TextPass::FULL) return carve_shared(h, base, t.R, t.Lp, t.Ls, t.mode == TextPass::SUFFIX);
+    SharedWs s;
+    s.w = carve_text(h, base, t.R, t.L);
+    s.total = s.w.total;
+    return s;
+}
+
+// The cache copy: rows [b, head, 0 .. L) of layer i's cache slabs (pitch Lmax positions) from the slabs the attention reads; the cache
+// (and the decode step) is bf16 in true units, the fp16 forms' slabs are fp16 behind sigma
+int keep_kv(vqs_qwen_handle* h, int i, const bf16_t* k, const bf16_t* v, void* d_kv, int R, int L, int Lmax, bool f16, float sigma, hipStream_t st) {
+    bf16_t* kc = (bf16_t*)d_kv + (size_t)(2 * i) * kv_slab(h, R, Lmax);
+    bf16_t* vc = kc + kv_slab(h, R, Lmax);
+    const size_t wb = (size_t)L * HDP * sizeof(bf16_t), pb = (size_t)Lmax * HDP * sizeof(bf16_t), nr = (size_t)R * h->c.t_kv_heads;
+    if (f16) {
+        if (nr > 65535) return fail(h, VQS_ERR_INVALID, "prefill: B * kv_heads exceeds 65535");
+        VQS_HIP(h, vqs::launch_f16_to_bf16_rows(k, kc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sigma, st), "keep K");
+        VQS_HIP(h, vqs::launch_f16_to_bf16_rows(v, vc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sigma, st), "keep V");
+    } else {
+        VQS_HIP(h, hipMemcpy2DAsync(kc, pb, k, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep K");
+        VQS_HIP(h, hipMemcpy2DAsync(vc, pb, v, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep V");
+    }
+    return VQS_OK;
+}
+
+// The entry points have validated every argument and the workspace size.
+int text_pass(vqs_qwen_handle* h, const TextPass& t, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const float* d_cos,
+              const float* d_sin, void* d_ws, hipStream_t st) {
     const vqs_qwen_config& c = h->c;
-    const TxtWs w = carve_text(h, (char*)d_ws, B, L);
-    if (ws_bytes < w.total) return fail(h, VQS_ERR_WORKSPACE, "score: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    const int TH = c.t_hidden, M = B * L, IQ = h->t_iq, IKV = h->t_ikv, XLD = h->t_xld;
+    const bool full = t.mode == TextPass::FULL, prefix = t.mode == TextPass::PREFIX, suffix = t.mode == TextPass::SUFFIX;
+    const int R = t.R, S = t.S, L = t.L;
+    const SharedWs ws = carve_pass(h, (char*)d_ws, t);
+    const TxtWs& w = ws.w;
+    const int TH = c.t_hidden, M = R * S, IQ = h->t_iq, IKV = h->t_ikv, XLD = h->t_xld;
     const float scale = 1.0f / sqrtf((float)h->t_hd);
-    VQS_W(embed, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * TH);
     // F: the range-safe fp16 forms (bind-time proof; every 16-bit tensor is fp16(T * sigma_T)); d_merged arrives in the same format
     const bool F = h->fp16_active != 0;
-    if (F && L < 8) return fail(h, VQS_ERR_INVALID, "score: the fp16 forms need L >= 8 (option fp16 = 0 runs any)");
-    VQS_HIP(h, vqs::launch_qwen_embed(d_input_ids, d_vis_slot, embed, (const bf16_t*)d_merged, w.hidden, M, TH, c.t_vocab, st, F, F ? 1.0f / h->m_out.sigma : 1.0f), "embed + splice");
-    VQS_HIP(h, hipMemsetAsync(w.ff, 0, (size_t)M * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
-    VQS_TAP("txt", -1, "emb", w.hidden, (size_t)M * TH);
-    const bool tail = h->tail_precise != 0 && (c.t_vocab % 4) == 0 && (c.t_hidden % 4) == 0;
-    if (tail)      // the tail's starting state: the embedding rows of the last positions (fp32 copies of bf16 values: exact)
-        VQS_HIP(h, vqs::launch_gather_rows_f32(w.hidden, d_last_row, w.t_h, B, TH, TH, st), "tail embed rows");
     const vqs_qwen_handle::LayerSites one{};
     const bool rope_in_gemm = F && h->rope_fused != 0 && h->t_hd == HDP;      // K12: 128-lane heads, scaled fp16 family (gemm_quad.inc ROPE)
+    const bool tail = !prefix && h->tail_precise != 0 && (c.t_vocab % 4) == 0 && (c.t_hidden % 4) == 0;
+
+    // ---- the steps in which the modes differ
+    struct KV { bf16_t *k, *v; };
+    const size_t pslab = full ? 0 : prefix_slab(h, t.U, t.Lp);
+    auto stored = [&](int i) {      // layer i's slabs of the prefix store
+        bf16_t* pk = (bf16_t*)t.d_pkv + (size_t)(2 * i) * pslab;
+        return KV{pk, pk + pslab};
+    };
+    // K/V destination: where layer i's q|k|v launch leaves the K and V heads of this pass's rows [R, Hkv, S, 128]
+    auto kv_dest = [&](int i) { return full ? KV{w.k, w.v} : prefix ? stored(i) : KV{ws.sk, ws.sv}; };
+    // K/V slabs for attention [R, Hkv, L, 128]: the launch's own output, or (SUFFIX) w.k / w.v assembled from every sample's prefix rows
+    // in the store and its suffix rows -- the tensors FULL has there, which the precise tail and the cache copy read as well
+    auto kv_slabs = [&](int i, KV own, KV& att) -> int {
+        att = suffix ? KV{w.k, w.v} : own;
+        if (suffix)
+            VQS_HIP(h, vqs::launch_qwen_kv_assemble(stored(i).k, stored(i).v, own.k, own.v, t.d_media_idx, w.k, w.v, R, t.U, c.t_kv_heads, t.Lp, t.Ls, st),
+                    "assemble K / V slabs");
+        return VQS_OK;
+    };
+    auto attention = [&](KV kv, float a_scale) -> int {
+        if (suffix) {      // rows [Lp, L) of the causal attention over L keys
+            vqs::AttnSuffixParams a{w.q, kv.k, kv.v, w.attn, t.d_seq_len, R, c.t_heads, c.t_kv_heads, L, t.Ls, t.Lp, a_scale};
+            a.f16 = F ? 1 : 0;
+            VQS_HIP(h, vqs::launch_attention_suffix(a, st), "suffix attention");
+            return VQS_OK;
+        }
+        vqs::AttnParams a{w.q, kv.k, kv.v, w.attn, nullptr, prefix ? ws.key_len : t.d_seq_len, R, c.t_heads, L, a_scale};
+        a.hd = HDP; a.Hkv = c.t_kv_heads; a.causal = 1; a.f16 = F ? 1 : 0;
+        VQS_HIP(h, vqs::launch_attention(a, st), prefix ? "prefix attention" : "attention");
+        return VQS_OK;
+    };
     auto norm = [&](const bf16_t* d, const bf16_t* g, const bf16_t* d2, bool store, float sd1, float sd2, float so, bool out_bf16, const char* what) -> int {
         if (F) VQS_HIP(h, vqs::launch_rmsnorm_f16s(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD, 1.0f / sd1, 1.0f / sd2, so, out_bf16), what);
         else VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD), what);
         return VQS_OK;
     };
+
+    VQS_W(embed, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * TH);
+    VQS_HIP(h, vqs::launch_qwen_embed(d_ids, d_vis_slot, embed, (const bf16_t*)d_merged, w.hidden, M, TH, c.t_vocab, st, F, F ? 1.0f / h->m_out.sigma : 1.0f), "embed + splice");
+    VQS_HIP(h, hipMemsetAsync(w.ff, 0, (size_t)M * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
+    VQS_TAP("txt", -1, "emb", w.hidden, (size_t)M * TH);
+    if (tail)      // the tail's starting state: the embedding rows of the last positions (fp32 copies of bf16 values: exact)
+        VQS_HIP(h, vqs::launch_gather_rows_f32(w.hidden, t.d_last_row, w.t_h, R, TH, TH, st), "tail embed rows");
+    if (prefix) VQS_HIP(h, hipMemsetD32Async((hipDeviceptr_t)ws.key_len, t.Lp, (size_t)R, st), "prefix key lengths");
 
     const bf16_t* pend = nullptr;
     const bf16_t* pend_attn = nullptr;   // attention delta the fp32 stream has not absorbed yet
@@ -921,6 +1047,7 @@ int score_impl(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_input_
         VQS_W(ln1, p + "input_layernorm.weight", TH);
         VQS_W(ln2, p + "post_attention_layernorm.weight", TH);
         const vqs_qwen_handle::LayerSites& sc = F ? h->t_sc[i] : one;
+        const KV own = kv_dest(i);
         VQS_RUN(norm(pend_attn ? pend_attn : pend, ln1, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, sc.x0.sigma, false, "input_layernorm"));
         VQS_TAP("txt", i, "h", w.hidden, (size_t)M * TH);            // the fp32 stream this layer starts from (input_layernorm stored it)
         VQS_RUN(tap2d(h, "txt", i, "xn0", w.xn, TH, M, XLD, st));
@@ -928,41 +1055,28 @@ int score_impl(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_input_
             GemmCall g{w.xn, F ? h->t_qkv_h[i] : h->t_qkv_w[i], nullptr};
             g.bias = h->t_qkv_b[i];
             g.M = M; g.N = IQ + 2 * IKV; g.K = TH; g.lda = XLD; g.ldw = TH; g.epi = vqs::EPI_HEADS;
-            g.S = L; g.H = c.t_heads; g.inner = IQ; g.hd = HDP; g.inner_kv = IKV; g.Hkv = c.t_kv_heads;
-            g.heads[0] = w.q; g.heads[1] = w.k; g.heads[2] = w.v;
+            g.S = S; g.H = c.t_heads; g.inner = IQ; g.hd = HDP; g.inner_kv = IKV; g.Hkv = c.t_kv_heads;
+            g.heads[0] = w.q; g.heads[1] = own.k; g.heads[2] = own.v;
             if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x0.sigma; g.out_scale = sc.qkv.sigma; }
             if (rope_in_gemm) { g.rope_cos = d_cos; g.rope_sin = d_sin; }
             VQS_RUN(run_gemm(h, g, {}, st, "qkv"));
         }
         if (!rope_in_gemm) {
             VQS_TAP("txt", i, "q0", w.q, (size_t)M * IQ);            // projection output, before the rotary embedding
-            VQS_TAP("txt", i, "k0", w.k, (size_t)M * IKV);
-            VQS_HIP(h, vqs::launch_rope_qk(w.q, w.k, d_cos, d_sin, B, c.t_heads, c.t_kv_heads, L, HDP, h->t_hd / 2, st, F), "rope");
+            VQS_TAP("txt", i, "k0", own.k, (size_t)M * IKV);
+            VQS_HIP(h, vqs::launch_rope_qk(w.q, own.k, d_cos, d_sin, R, c.t_heads, c.t_kv_heads, S, HDP, h->t_hd / 2, st, F), "rope");
         }
-        VQS_TAP("txt", i, "q", w.q, (size_t)M * IQ);                 // after the rotary embedding, head-major [B, heads, L, 128]
-        VQS_TAP("txt", i, "k", w.k, (size_t)M * IKV);
-        VQS_TAP("txt", i, "v", w.v, (size_t)M * IKV);
-        if (d_kv) {   // rows [b, head, 0 .. L) of the cache slabs (pitch Lmax positions); the cache (and the decode step) is bf16 in true units
-            bf16_t* kc = (bf16_t*)d_kv + (size_t)(2 * i) * kv_slab(h, B, Lmax);
-            bf16_t* vc = kc + kv_slab(h, B, Lmax);
-            const size_t wb = (size_t)L * HDP * sizeof(bf16_t), pb = (size_t)Lmax * HDP * sizeof(bf16_t), nr = (size_t)B * c.t_kv_heads;
-            if (F) {
-                if (nr > 65535) return fail(h, VQS_ERR_INVALID, "prefill: B * kv_heads exceeds 65535");
-                VQS_HIP(h, vqs::launch_f16_to_bf16_rows(w.k, kc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep K");
-                VQS_HIP(h, vqs::launch_f16_to_bf16_rows(w.v, vc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep V");
-            } else {
-                VQS_HIP(h, hipMemcpy2DAsync(kc, pb, w.k, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep K");
-                VQS_HIP(h, hipMemcpy2DAsync(vc, pb, w.v, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep V");
-            }
-        }
-        {
-            vqs::AttnParams a{w.q, w.k, w.v, w.attn, nullptr, d_seq_len, B, c.t_heads, L, scale / (sc.qkv.sigma * sc.qkv.sigma)};
-            a.hd = HDP; a.Hkv = c.t_kv_heads; a.causal = 1; a.f16 = F ? 1 : 0;
-            VQS_HIP(h, vqs::launch_attention(a, st), "attention");
-        }
+        KV att;
+        VQS_RUN(kv_slabs(i, own, att));
+        VQS_TAP("txt", i, "q", w.q, (size_t)M * IQ);                 // after the rotary embedding, head-major [R, heads, S, 128]
+        VQS_TAP("txt", i, "k", att.k, (size_t)R * L * IKV);          // what the attention reads: [R, kv_heads, L, 128]
+        VQS_TAP("txt", i, "v", att.v, (size_t)R * L * IKV);
+        if (t.d_kv) VQS_RUN(keep_kv(h, i, att.k, att.v, t.d_kv, R, L, t.Lmax, F, sc.qkv.sigma, st));
+        if (prefix && i == c.t_layers - 1) return VQS_OK;      // PREFIX exit: the last layer's K / V are all the suffix pass reads of the prefix
+        VQS_RUN(attention(att, scale / (sc.qkv.sigma * sc.qkv.sigma)));
         VQS_TAP("txt", i, "attn", w.attn, (size_t)M * IQ);
-        if (tail)      // this layer's K / V are in w.k / w.v until the next layer's qkv launch
-            VQS_RUN(tail_layer(h, w, i, ln1, ln2, d_seq_len, d_last_row, d_cos, d_sin, B, L, i == 0, st, F, sc.qkv.sigma));
+        if (tail)      // this layer's K / V are in w.k / w.v until the next layer's qkv launch (SUFFIX: assemble)
+            VQS_RUN(tail_layer(h, w, i, ln1, ln2, t.d_seq_len, t.d_last_row, d_cos, d_sin, R, L, i == 0, st, F, sc.qkv.sigma));
         {
             GemmCall g{w.attn, F ? h->t_o_h[i] : h->t_o_w[i], w.delta};
             g.M = M; g.N = TH; g.K = IQ; g.lda = IQ; g.ldw = IQ; g.ldc = TH; g.epi = vqs::EPI_BF16;
@@ -989,23 +1103,67 @@ int score_impl(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_input_
         }
         VQS_TAP("txt", i, "d_mlp", w.delta2, (size_t)M * TH);
     }
+    // ---- tail and head (FULL and SUFFIX; PREFIX left the loop)
     VQS_W(fin, "model.language_model.norm.weight", TH);
     VQS_W(head, "lm_head.weight", (int64_t)c.t_vocab * TH);
     // the final norm's operand is bf16 in true units either way: lm_head (bf16 weights, fp32 logits) reads it when the tail is off
     VQS_RUN(norm(pend_attn ? pend_attn : pend, fin, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, 1.0f, true, "final norm"));
     VQS_TAP("txt", -1, "h_out", w.hidden, (size_t)M * TH);
     VQS_RUN(tap2d(h, "txt", -1, "xnf", w.xn, TH, M, XLD, st));
-    if (tail) {
-        VQS_RUN(tail_head(h, w, fin, head, d_logits, B, st));
-        return VQS_OK;
-    }
-    VQS_HIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, d_last_row, w.last, B, TH, XLD, TH, st), "last positions");
+    if (tail) return tail_head(h, w, fin, head, t.d_logits, R, st);
+    VQS_HIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, t.d_last_row, w.last, R, TH, XLD, TH, st), "last positions");
     {
-        GemmCall g{w.last, head, d_logits};
-        g.M = B; g.N = c.t_vocab; g.K = TH; g.lda = TH; g.ldw = TH; g.ldc = c.t_vocab; g.epi = vqs::EPI_F32;
+        GemmCall g{w.last, head, t.d_logits};
+        g.M = R; g.N = c.t_vocab; g.K = TH; g.lda = TH; g.ldw = TH; g.ldc = c.t_vocab; g.epi = vqs::EPI_F32;
         VQS_RUN(run_gemm(h, g, {}, st, "lm_head"));
     }
     return VQS_OK;
+}
+
+// vqs_qwen_score / vqs_qwen_prefill (cached: the pass also fills the decode cache)
+int full_entry(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+               const int32_t* d_last_row, const float* d_cos, const float* d_sin, int32_t B, int32_t L, float* d_logits, void* d_ws, size_t ws_bytes,
+               void* d_kv, size_t kv_bytes, int32_t Lmax, bool cached, void* stream) {
+    if (!h) return VQS_ERR_INVALID;
+    if (cached) {
+        if (!d_kv || Lmax < L || kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return fail(h, VQS_ERR_WORKSPACE, "prefill: KV cache missing or too small");
+        if (Lmax > VQS_QWEN_MAX_CACHE_POSITIONS)      // the decode step's one-row attention keeps Lmax fp32 scores in LDS: refuse BEFORE the prefill is spent
+            return fail(h, VQS_ERR_INVALID, "prefill: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
+    }
+    if (!h->bound) return fail(h, VQS_ERR_STATE, "score: weights not bound");
+    if (!d_merged || !d_ids || !d_vis_slot || !d_seq_len || !d_last_row || !d_cos || !d_sin || !d_logits || !d_ws)
+        return fail(h, VQS_ERR_INVALID, "score: null argument");
+    if (B <= 0 || L <= 0) return fail(h, VQS_ERR_INVALID, "score: need B > 0, L > 0");
+    TextPass t{TextPass::FULL, B, L, L};
+    t.d_kv = cached ? d_kv : nullptr; t.Lmax = Lmax; t.d_seq_len = d_seq_len; t.d_last_row = d_last_row; t.d_logits = d_logits;
+    if (ws_bytes < carve_pass(h, nullptr, t).total) return fail(h, VQS_ERR_WORKSPACE, "score: workspace too small");
+    if (h->fp16_active && L < 8) return fail(h, VQS_ERR_INVALID, "score: the fp16 forms need L >= 8 (option fp16 = 0 runs any)");
+    return text_pass(h, t, d_merged, d_ids, d_vis_slot, d_cos, d_sin, d_ws, (hipStream_t)stream);
+}
+
+int suffix_entry(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                 const int32_t* d_last_row, const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int32_t B, int32_t Lp, int32_t Ls,
+                 const void* d_pkv, int32_t U, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv, size_t kv_bytes,
+                 int32_t Lmax, bool cached, void* stream) {
+    if (!h) return VQS_ERR_INVALID;
+    // sizes first: an invalid shape is refused whatever else is wrong with the call
+    if (!suffix_shape_ok(B, Lp, Ls) || !prefix_shape_ok(U, Lp))
+        return fail(h, VQS_ERR_INVALID, "score_suffix: need B, U > 0, Lp a multiple of 32 (>= 32), Ls >= 8, Lp + Ls <= " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS));
+    if (cached && Lmax > VQS_QWEN_MAX_CACHE_POSITIONS)
+        return fail(h, VQS_ERR_INVALID, "prefill_suffix: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
+    if (!h->bound) return fail(h, VQS_ERR_STATE, "score_suffix: weights not bound");
+    if (!d_merged || !d_ids || !d_vis_slot || !d_seq_len || !d_last_row || !d_cos || !d_sin || !d_media_idx || !d_pkv || !d_logits || !d_ws)
+        return fail(h, VQS_ERR_INVALID, "score_suffix: null argument");
+    if (pkv_bytes < vqs_qwen_prefix_kv_bytes(h, U, Lp)) return fail(h, VQS_ERR_WORKSPACE, "score_suffix: prefix store too small");
+    if (cached) {
+        if (!d_kv || Lmax < Lp + Ls || kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return fail(h, VQS_ERR_WORKSPACE, "prefill_suffix: KV cache missing or too small");
+        if (h->fp16_active && (int64_t)B * h->c.t_kv_heads > 65535) return fail(h, VQS_ERR_INVALID, "prefill_suffix: B * kv_heads exceeds 65535");
+    }
+    TextPass t{TextPass::SUFFIX, B, Ls, Lp + Ls};
+    t.U = U; t.Lp = Lp; t.Ls = Ls; t.d_media_idx = d_media_idx; t.d_pkv = d_pkv; t.d_kv = cached ? d_kv : nullptr; t.Lmax = Lmax;
+    t.d_seq_len = d_seq_len; t.d_last_row = d_last_row; t.d_logits = d_logits;
+    if (ws_bytes < carve_pass(h, nullptr, t).total) return fail(h, VQS_ERR_WORKSPACE, "shared prefix: workspace too small");
+    return text_pass(h, t, d_merged, d_ids, d_vis_slot, d_cos, d_sin, d_ws, (hipStream_t)stream);
 }
 
 struct DecWs {
@@ -1030,16 +1188,9 @@ DecWs carve_decode(const vqs_qwen_handle* h, char* base, int B) {
     w.attn = cv.take<bf16_t>(b * h->t_iq);
     w.ff = cv.take<bf16_t>(b * h->t_ffld);
     w.neg1 = cv.take<int>(b);
-    {   // widest partial set of the step's four linears: slices(N, K) x N fp32 per row, by the SAME rule decode_linear launches with
-        // (a hand-written bound missed gate|up with two slices -- Qwen2.5-VL-3B's 2048 / 11008 -- and every step failed)
-        const int QN = h->t_iq + 2 * h->t_ikv;
-        size_t widest = (size_t)decode_slices(QN, c.t_hidden) * QN;                                       // qkv
-        widest = std::max(widest, (size_t)decode_slices(c.t_hidden, h->t_iq) * c.t_hidden);               // o_proj
-        widest = std::max(widest, (size_t)decode_slices(2 * h->t_mlp_p, c.t_hidden) * 2 * h->t_mlp_p);    // gate|up
-        widest = std::max(widest, (size_t)decode_slices(c.t_hidden, h->t_ffld) * c.t_hidden);             // down_proj
-        w.part_bytes = b * widest * sizeof(float);
-        w.part = cv.take<float>(b * widest);
-    }
+    const size_t widest = widest_partials(h, false);
+    w.part_bytes = b * widest * sizeof(float);
+    w.part = cv.take<float>(b * widest);
     w.total = cv.total();
     return w;
 }
@@ -1052,12 +1203,8 @@ DecWs carve_decode(const vqs_qwen_handle* h, char* base, int B) {
 // gate|up columns) and rounds to bf16.  Falls back to the persistent kernel (same bits) when the form does not apply (B > 128).
 int decode_linear(vqs_qwen_handle* h, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias, bf16_t* out, int ldo, int B,
                   int N, int K, int gated, const DecWs& w, hipStream_t st, const char* what) {
-    const int sk = decode_slices(N, K);
-    if ((size_t)sk * B * N * sizeof(float) > w.part_bytes) return fail(h, VQS_ERR_WORKSPACE, std::string(what) + ": decode scratch too small");
-    GemmCall g{A, W, w.part};      // K slices as batch entries, fp32 partials
-    g.M = B; g.N = N; g.K = K / sk; g.lda = lda; g.ldw = ldw; g.ldc = N; g.epi = vqs::EPI_F32;
-    g.batch = sk; g.sA = K / sk; g.sW = K / sk; g.sC = (long long)B * N;
-    VQS_RUN(run_gemm(h, g, {}, st, what));
+    int sk;
+    VQS_RUN(sliced_linear(h, A, lda, W, ldw, B, N, K, w.part, w.part_bytes, "decode", st, what, &sk));
     VQS_HIP(h, vqs::launch_reduce_slices_act(w.part, sk, (long long)B * N, B, N, N, bias, gated, out, ldo, st), std::string("reduce ") + what);
     return VQS_OK;
 }
@@ -1068,8 +1215,8 @@ extern "C" {
 int vqs_qwen_score(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_input_ids, const int32_t* d_vis_slot,
                    const int32_t* d_seq_len, const int32_t* d_last_row, const float* d_cos, const float* d_sin, int32_t B,
                    int32_t L, float* d_logits, void* d_ws, size_t ws_bytes, void* stream) {
-    return score_impl(h, d_merged, d_input_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, B, L, d_logits, d_ws, ws_bytes, stream,
-                      nullptr, 0);
+    return full_entry(h, d_merged, d_input_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, B, L, d_logits, d_ws, ws_bytes, nullptr, 0, 0, false,
+                      stream);
 }
 
 size_t vqs_qwen_kv_bytes(const vqs_qwen_handle* h, int32_t B, int32_t Lmax) {
@@ -1080,12 +1227,8 @@ size_t vqs_qwen_kv_bytes(const vqs_qwen_handle* h, int32_t B, int32_t Lmax) {
 int vqs_qwen_prefill(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_input_ids, const int32_t* d_vis_slot,
                      const int32_t* d_seq_len, const int32_t* d_last_row, const float* d_cos, const float* d_sin, int32_t B,
                      int32_t L, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv, size_t kv_bytes, int32_t Lmax, void* stream) {
-    if (!h) return VQS_ERR_INVALID;
-    if (!d_kv || Lmax < L || kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return fail(h, VQS_ERR_WORKSPACE, "prefill: KV cache missing or too small");
-    if (Lmax > VQS_QWEN_MAX_CACHE_POSITIONS)      // the decode step's one-row attention keeps Lmax fp32 scores in LDS: refuse BEFORE the prefill is spent
-        return fail(h, VQS_ERR_INVALID, "prefill: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
-    return score_impl(h, d_merged, d_input_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, B, L, d_logits, d_ws, ws_bytes, stream, d_kv,
-                      Lmax);
+    return full_entry(h, d_merged, d_input_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, B, L, d_logits, d_ws, ws_bytes, d_kv, kv_bytes, Lmax,
+                      true, stream);
 }
 
 size_t vqs_qwen_decode_workspace_bytes(const vqs_qwen_handle* h, int32_t B) {
@@ -1155,186 +1298,6 @@ int vqs_qwen_decode(vqs_qwen_handle* h, const int32_t* d_ids, const int32_t* d_l
     return VQS_OK;
 }
 
-}  // extern "C"
-
-namespace {
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Shared prompt prefix (include/vqs_qwen.h vqs_qwen_prefix / vqs_qwen_score_suffix / vqs_qwen_prefill_suffix).  The first Lp rows of
-// every prompt about one medium are the same tokens at the same positions, and the language model is causal: their K / V in every layer
-// do not depend on the question.  The prefix pass runs score_impl's layer sequence over U prefixes and leaves each layer's K (rotated) and
-// V in the prefix store, in the tensors the attention reads (bf16, or fp16 behind the layer's q|k|v scale).  The suffix pass runs the
-// same sequence over the suffix rows only; per layer, launch_qwen_kv_assemble builds the [B, Hkv, Lp + Ls, 128] slabs score_impl has in
-// w.k / w.v (prefix rows from the store, suffix rows from the q|k|v launch), and the precise tail, the cache copy and the decode step read
-// them unchanged.  Every launch is row-independent (GEMM forms are a function of the weight's shape, never of M; norms, embedding and rope
-// are per row) except attention, whose rows couple through the wave-uniform deferred rescale: Lp is a multiple of 32 so that the prefix
-// pass (attn_fwd_hd_kernel over Lp rows) and the suffix pass (attn_suffix_hd_kernel over rows [Lp, L)) hold the same 32-row waves as
-// the full kernel over L rows.  Result: bitwise the logits and cache of vqs_qwen_score / vqs_qwen_prefill over the whole prompts.
-// ---------------------------------------------------------------------------------------------------------------------------------
-inline size_t prefix_slab(const vqs_qwen_handle* h, int U, int Lp) { return (size_t)U * h->c.t_kv_heads * (size_t)Lp * HDP; }
-
-struct SharedWs {
-    TxtWs w;
-    bf16_t *sk = nullptr, *sv = nullptr;   // suffix pass: the suffix rows' own K / V [B, Hkv, Ls, 128]
-    int* key_len = nullptr;                // prefix pass: Lp per prefix
-    size_t total = 0;
-};
-SharedWs carve_shared(const vqs_qwen_handle* h, char* base, int R, int Lp, int Ls, bool suffix) {
-    SharedWs s;
-    s.w = carve_text(h, base, R, suffix ? Lp + Ls : Lp);
-    Carver cv{base};
-    cv.off = s.w.total;
-    if (suffix) {
-        s.sk = cv.take<bf16_t>((size_t)R * Ls * h->t_ikv);
-        s.sv = cv.take<bf16_t>((size_t)R * Ls * h->t_ikv);
-    } else {
-        s.key_len = cv.take<int>((size_t)R);
-    }
-    s.total = cv.total();
-    return s;
-}
-bool prefix_shape_ok(int U, int Lp) { return U > 0 && Lp >= 32 && (Lp % 32) == 0 && Lp <= VQS_QWEN_MAX_CACHE_POSITIONS; }
-bool suffix_shape_ok(int B, int Lp, int Ls) {
-    return B > 0 && Lp >= 32 && (Lp % 32) == 0 && Ls >= 8 && (int64_t)Lp + Ls <= VQS_QWEN_MAX_CACHE_POSITIONS;
-}
-
-// suffix == false: the prefix pass (R = U prompt prefixes of Lp rows); true: the suffix pass (R = B suffixes of Ls rows behind the prefixes
-// of media d_media_idx), d_kv != nullptr also fills the decode cache
-int shared_impl(vqs_qwen_handle* h, bool suffix, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
-                const int32_t* d_last_row, const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int R, int U, int Lp, int Ls,
-                const void* d_pkv, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv, int Lmax, hipStream_t st) {
-    const vqs_qwen_config& c = h->c;
-    const int S = suffix ? Ls : Lp;                // rows per sample of this pass
-    const int L = suffix ? Lp + Ls : Lp;           // keys per sample of its attention
-    const SharedWs sw = carve_shared(h, (char*)d_ws, R, Lp, Ls, suffix);
-    if (ws_bytes < sw.total) return fail(h, VQS_ERR_WORKSPACE, "shared prefix: workspace too small");
-    const TxtWs& w = sw.w;
-    const int TH = c.t_hidden, M = R * S, IKV = h->t_ikv, XLD = h->t_xld;
-    const float scale = 1.0f / sqrtf((float)h->t_hd);
-    const bool F = h->fp16_active != 0;
-    VQS_W(embed, "model.language_model.embed_tokens.weight", (int64_t)c.t_vocab * TH);
-    VQS_HIP(h, vqs::launch_qwen_embed(d_ids, d_vis_slot, embed, (const bf16_t*)d_merged, w.hidden, M, TH, c.t_vocab, st, F, F ? 1.0f / h->m_out.sigma : 1.0f), "embed + splice");
-    VQS_HIP(h, hipMemsetAsync(w.ff, 0, (size_t)M * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
-    const bool tail = suffix && h->tail_precise != 0 && (c.t_vocab % 4) == 0 && (c.t_hidden % 4) == 0;
-    if (tail) VQS_HIP(h, vqs::launch_gather_rows_f32(w.hidden, d_last_row, w.t_h, R, TH, TH, st), "tail embed rows");
-    if (!suffix) VQS_HIP(h, hipMemsetD32Async((hipDeviceptr_t)sw.key_len, Lp, (size_t)R, st), "prefix key lengths");
-    const vqs_qwen_handle::LayerSites one{};
-    const bool rope_in_gemm = F && h->rope_fused != 0 && h->t_hd == HDP;
-    auto norm = [&](const bf16_t* d, const bf16_t* g, const bf16_t* d2, bool store, float sd1, float sd2, float so, bool out_bf16, const char* what) -> int {
-        if (F) VQS_HIP(h, vqs::launch_rmsnorm_f16s(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD, 1.0f / sd1, 1.0f / sd2, so, out_bf16), what);
-        else VQS_HIP(h, vqs::launch_rmsnorm(w.hidden, d, g, w.xn, M, TH, c.t_eps, st, d2, store, XLD), what);
-        return VQS_OK;
-    };
-    const bf16_t* pend = nullptr;
-    const bf16_t* pend_attn = nullptr;
-    float s_pend = 1.0f, s_pend_attn = 1.0f;
-    for (int i = 0; i < c.t_layers; ++i) {
-        const std::string p = "model.language_model.layers." + std::to_string(i) + ".";
-        VQS_W(ln1, p + "input_layernorm.weight", TH);
-        VQS_W(ln2, p + "post_attention_layernorm.weight", TH);
-        const vqs_qwen_handle::LayerSites& sc = F ? h->t_sc[i] : one;
-        bf16_t* pk = (bf16_t*)d_pkv + (size_t)(2 * i) * prefix_slab(h, U, Lp);
-        bf16_t* pv = pk + prefix_slab(h, U, Lp);
-        bf16_t* kout = suffix ? sw.sk : pk;
-        bf16_t* vout = suffix ? sw.sv : pv;
-        VQS_RUN(norm(pend_attn ? pend_attn : pend, ln1, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, sc.x0.sigma, false, "input_layernorm"));
-        {
-            GemmCall g{w.xn, F ? h->t_qkv_h[i] : h->t_qkv_w[i], nullptr};
-            g.bias = h->t_qkv_b[i];
-            g.M = M; g.N = h->t_iq + 2 * IKV; g.K = TH; g.lda = XLD; g.ldw = TH; g.epi = vqs::EPI_HEADS;
-            g.S = S; g.H = c.t_heads; g.inner = h->t_iq; g.hd = HDP; g.inner_kv = IKV; g.Hkv = c.t_kv_heads;
-            g.heads[0] = w.q; g.heads[1] = kout; g.heads[2] = vout;
-            if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x0.sigma; g.out_scale = sc.qkv.sigma; }
-            if (rope_in_gemm) { g.rope_cos = d_cos; g.rope_sin = d_sin; }
-            VQS_RUN(run_gemm(h, g, {}, st, "qkv"));
-        }
-        if (!rope_in_gemm) VQS_HIP(h, vqs::launch_rope_qk(w.q, kout, d_cos, d_sin, R, c.t_heads, c.t_kv_heads, S, HDP, h->t_hd / 2, st, F), "rope");
-        if (!suffix && i == c.t_layers - 1) break;     // the last layer's K / V are all the suffix pass reads of the prefix
-        const float a_scale = scale / (sc.qkv.sigma * sc.qkv.sigma);
-        if (suffix) {
-            VQS_HIP(h, vqs::launch_qwen_kv_assemble(pk, pv, sw.sk, sw.sv, d_media_idx, w.k, w.v, R, U, c.t_kv_heads, Lp, Ls, st), "assemble K / V slabs");
-            if (d_kv) {   // as score_impl: rows [b, head, 0 .. L) of the cache slabs, bf16 in true units
-                bf16_t* kc = (bf16_t*)d_kv + (size_t)(2 * i) * kv_slab(h, R, Lmax);
-                bf16_t* vc = kc + kv_slab(h, R, Lmax);
-                const size_t wb = (size_t)L * HDP * sizeof(bf16_t), pb = (size_t)Lmax * HDP * sizeof(bf16_t), nr = (size_t)R * c.t_kv_heads;
-                if (F) {
-                    if (nr > 65535) return fail(h, VQS_ERR_INVALID, "prefill: B * kv_heads exceeds 65535");
-                    VQS_HIP(h, vqs::launch_f16_to_bf16_rows(w.k, kc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep K");
-                    VQS_HIP(h, vqs::launch_f16_to_bf16_rows(w.v, vc, (int)nr, (long long)L * HDP, (long long)L * HDP, (long long)Lmax * HDP, 1.0f / sc.qkv.sigma, st), "keep V");
-                } else {
-                    VQS_HIP(h, hipMemcpy2DAsync(kc, pb, w.k, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep K");
-                    VQS_HIP(h, hipMemcpy2DAsync(vc, pb, w.v, wb, wb, nr, hipMemcpyDeviceToDevice, st), "keep V");
-                }
-            }
-            vqs::AttnSuffixParams a{w.q, w.k, w.v, w.attn, d_seq_len, R, c.t_heads, c.t_kv_heads, L, Ls, Lp, a_scale};
-            a.f16 = F ? 1 : 0;
-            VQS_HIP(h, vqs::launch_attention_suffix(a, st), "suffix attention");
-        } else {
-            vqs::AttnParams a{w.q, pk, pv, w.attn, nullptr, sw.key_len, R, c.t_heads, Lp, a_scale};
-            a.hd = HDP; a.Hkv = c.t_kv_heads; a.causal = 1; a.f16 = F ? 1 : 0;
-            VQS_HIP(h, vqs::launch_attention(a, st), "prefix attention");
-        }
-        if (tail) VQS_RUN(tail_layer(h, w, i, ln1, ln2, d_seq_len, d_last_row, d_cos, d_sin, R, L, i == 0, st, F, sc.qkv.sigma));
-        {
-            GemmCall g{w.attn, F ? h->t_o_h[i] : h->t_o_w[i], w.delta};
-            g.M = M; g.N = TH; g.K = h->t_iq; g.lda = h->t_iq; g.ldw = h->t_iq; g.ldc = TH; g.epi = vqs::EPI_BF16;
-            if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.qkv.sigma; g.out_scale = sc.dattn.sigma; }
-            VQS_RUN(run_gemm(h, g, {}, st, "o_proj"));
-        }
-        VQS_RUN(norm(w.delta, ln2, nullptr, false, sc.dattn.sigma, 1.0f, sc.x1.sigma, false, "post_attention_layernorm"));
-        pend_attn = w.delta; s_pend_attn = sc.dattn.sigma;
-        {
-            GemmCall g{w.xn, F ? h->t_gu_h[i] : h->t_gu_w[i], w.ff};
-            g.M = M; g.N = 2 * h->t_mlp_p; g.K = TH; g.lda = XLD; g.ldw = XLD; g.ldc = h->t_ffld; g.epi = vqs::EPI_GATED; g.gate_act = 1;
-            if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.x1.sigma; g.out_scale = sc.act.sigma; }
-            VQS_RUN(run_gemm(h, g, {}, st, "gate|up"));
-        }
-        {
-            GemmCall g{w.ff, F ? h->t_down_h[i] : h->t_down_w[i], w.delta2};
-            g.M = M; g.N = TH; g.K = h->t_ffld; g.lda = h->t_ffld; g.ldw = h->t_ffld; g.ldc = TH; g.epi = vqs::EPI_BF16;
-            if (F) { g.f16 = 3; g.acc_scale = 1.0f / sc.act.sigma; g.out_scale = sc.dmlp.sigma; }
-            VQS_RUN(run_gemm(h, g, {}, st, "down_proj"));
-            pend = w.delta2; s_pend = sc.dmlp.sigma;
-        }
-    }
-    if (!suffix) return VQS_OK;
-    VQS_W(fin, "model.language_model.norm.weight", TH);
-    VQS_W(head, "lm_head.weight", (int64_t)c.t_vocab * TH);
-    VQS_RUN(norm(pend_attn ? pend_attn : pend, fin, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, 1.0f, true, "final norm"));
-    if (tail) return tail_head(h, w, fin, head, d_logits, R, st);
-    VQS_HIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, d_last_row, w.last, R, TH, XLD, TH, st), "last positions");
-    {
-        GemmCall g{w.last, head, d_logits};
-        g.M = R; g.N = c.t_vocab; g.K = TH; g.lda = TH; g.ldw = TH; g.ldc = c.t_vocab; g.epi = vqs::EPI_F32;
-        VQS_RUN(run_gemm(h, g, {}, st, "lm_head"));
-    }
-    return VQS_OK;
-}
-
-int suffix_entry(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
-                 const int32_t* d_last_row, const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int32_t B, int32_t Lp, int32_t Ls,
-                 const void* d_pkv, int32_t U, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv, size_t kv_bytes,
-                 int32_t Lmax, bool cached, void* stream) {
-    if (!h) return VQS_ERR_INVALID;
-    // sizes first: an invalid shape is refused whatever else is wrong with the call
-    if (!suffix_shape_ok(B, Lp, Ls) || !prefix_shape_ok(U, Lp))
-        return fail(h, VQS_ERR_INVALID, "score_suffix: need B, U > 0, Lp a multiple of 32 (>= 32), Ls >= 8, Lp + Ls <= " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS));
-    if (cached && Lmax > VQS_QWEN_MAX_CACHE_POSITIONS)
-        return fail(h, VQS_ERR_INVALID, "prefill_suffix: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
-    if (!h->bound) return fail(h, VQS_ERR_STATE, "score_suffix: weights not bound");
-    if (!d_merged || !d_ids || !d_vis_slot || !d_seq_len || !d_last_row || !d_cos || !d_sin || !d_media_idx || !d_pkv || !d_logits || !d_ws)
-        return fail(h, VQS_ERR_INVALID, "score_suffix: null argument");
-    if (pkv_bytes < vqs_qwen_prefix_kv_bytes(h, U, Lp)) return fail(h, VQS_ERR_WORKSPACE, "score_suffix: prefix store too small");
-    if (cached) {
-        if (!d_kv || Lmax < Lp + Ls || kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return fail(h, VQS_ERR_WORKSPACE, "prefill_suffix: KV cache missing or too small");
-        if (h->fp16_active && (int64_t)B * h->c.t_kv_heads > 65535) return fail(h, VQS_ERR_INVALID, "prefill_suffix: B * kv_heads exceeds 65535");
-    }
-    return shared_impl(h, true, d_merged, d_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, d_media_idx, B, U, Lp, Ls, d_pkv, pkv_bytes, d_logits,
-                       d_ws, ws_bytes, cached ? d_kv : nullptr, Lmax, (hipStream_t)stream);
-}
-}  // namespace
-
-extern "C" {
-
 size_t vqs_qwen_prefix_kv_bytes(const vqs_qwen_handle* h, int32_t U, int32_t Lp) {
     if (!h || !prefix_shape_ok(U, Lp)) return 0;
     return (size_t)2 * h->c.t_layers * prefix_slab(h, U, Lp) * sizeof(bf16_t);
@@ -1358,8 +1321,10 @@ int vqs_qwen_prefix(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_i
     if (!h->bound) return fail(h, VQS_ERR_STATE, "prefix: weights not bound");
     if (!d_merged || !d_ids || !d_vis_slot || !d_cos || !d_sin || !d_pkv || !d_ws) return fail(h, VQS_ERR_INVALID, "prefix: null argument");
     if (pkv_bytes < vqs_qwen_prefix_kv_bytes(h, U, Lp)) return fail(h, VQS_ERR_WORKSPACE, "prefix: prefix store too small");
-    return shared_impl(h, false, d_merged, d_ids, d_vis_slot, nullptr, nullptr, d_cos, d_sin, nullptr, U, U, Lp, 0, d_pkv, pkv_bytes, nullptr, d_ws,
-                       ws_bytes, nullptr, 0, (hipStream_t)stream);
+    TextPass t{TextPass::PREFIX, U, Lp, Lp};
+    t.U = U; t.Lp = Lp; t.d_pkv = d_pkv;
+    if (ws_bytes < carve_pass(h, nullptr, t).total) return fail(h, VQS_ERR_WORKSPACE, "shared prefix: workspace too small");
+    return text_pass(h, t, d_merged, d_ids, d_vis_slot, d_cos, d_sin, d_ws, (hipStream_t)stream);
 }
 
 int vqs_qwen_score_suffix(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,

@@ -155,53 +155,53 @@ class QwenEngine:
                                                         _stream_ptr()), "vqs_qwen_encode_vision")
             return out
 
-    def score_logits(self, merged: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor,
-                     grids: Sequence[Tuple[int, int, int]]) -> torch.Tensor:
-        """-> fp32 [B, vocab]: logits of the last valid position of every sample (= scores[0] of HF generate)."""
+    def _upload(self, lay, keys=("vis_slot", "seq_len", "last_row", "cos", "sin")):
+        """-> device copies of the named tensors of a text_layout / shared_prefix_plan result."""
+        return {k: lay[k].to(self.device).contiguous() for k in keys}
+
+    def _decode_state(self, lay, kv, seq_len, Lmax):
+        """-> the state decode() advances: the cache `kv`, `seq_len` (device) and what `lay` (layout or plan) says about the next position."""
+        # len_host_max: the longest sample's length, tracked on the HOST -- decode() checks the cache bound without reading the device
+        # tensor (round 3 did `int(state["len"].max())` per step: a device sync that serialised the host's ~400 launches per step
+        # with the GPU's work; the decode kernels themselves ignore / clamp a length outside the cache, qwen_decode.hip)
+        # pos: the next token's M-RoPE position per axis, kept ON THE DEVICE -- decode() derives its cos / sin tables there (a few
+        # tiny launches) instead of on the host: the host tables cost two blocking H2D copies per step, each a stream synchronise
+        # (PyTorch syncs after a pageable copy), i.e. the host's launches never overlapped the GPU's work, and torch's CPU thread
+        # pool stalled a step by 70 ms now and then (profiles/r4_call15_*)
+        return {"kv": kv, "len": seq_len.clone(), "Lmax": Lmax, "B": seq_len.shape[0], "pos": lay["next_pos"].clone().to(self.device),
+                "steps": 0, "len_host_max": int(lay["seq_len"].max())}
+
+    def _full_pass(self, merged, input_ids, attention_mask, grids, max_new_tokens):
+        """vqs_qwen_score (max_new_tokens None) or vqs_qwen_prefill over the whole prompts -> (logits, decode state or None)."""
         lay = text_layout(self.cfg, input_ids.cpu(), attention_mask.cpu(), grids)
         with torch.cuda.device(self.device):
             dev = self.device
             B, L = input_ids.shape
             ids = input_ids.to(dev, torch.int32).contiguous()
-            t = {k: lay[k].to(dev) for k in ("vis_slot", "seq_len", "last_row", "cos", "sin")}
+            t = self._upload(lay)
             logits = torch.empty(B, self.cfg.text.vocab, dtype=torch.float32, device=dev)
             self._merged_matches_mode(merged)
             ws = self._workspace(self.lib.vqs_qwen_score_workspace_bytes(self._h, B, L))
-            self._check(self.lib.vqs_qwen_score(self._h, merged.contiguous().data_ptr(), ids.data_ptr(), t["vis_slot"].data_ptr(),
-                                                t["seq_len"].data_ptr(), t["last_row"].data_ptr(), t["cos"].data_ptr(),
-                                                t["sin"].data_ptr(), B, L, logits.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                _stream_ptr()), "vqs_qwen_score")
-            return logits
+            args = [self._h, merged.contiguous().data_ptr(), ids.data_ptr(), t["vis_slot"].data_ptr(), t["seq_len"].data_ptr(),
+                    t["last_row"].data_ptr(), t["cos"].data_ptr(), t["sin"].data_ptr(), B, L, logits.data_ptr(), ws.data_ptr(), ws.numel()]
+            if max_new_tokens is None:
+                self._check(self.lib.vqs_qwen_score(*args, _stream_ptr()), "vqs_qwen_score")
+                return logits, None
+            Lmax = L + max(int(max_new_tokens) - 1, 0)
+            kv = torch.empty(self.lib.vqs_qwen_kv_bytes(self._h, B, Lmax), dtype=torch.uint8, device=dev)
+            self._check(self.lib.vqs_qwen_prefill(*args, kv.data_ptr(), kv.numel(), Lmax, _stream_ptr()), "vqs_qwen_prefill")
+            return logits, self._decode_state(lay, kv, t["seq_len"], Lmax)
+
+    def score_logits(self, merged: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor,
+                     grids: Sequence[Tuple[int, int, int]]) -> torch.Tensor:
+        """-> fp32 [B, vocab]: logits of the last valid position of every sample (= scores[0] of HF generate)."""
+        return self._full_pass(merged, input_ids, attention_mask, grids, None)[0]
 
     def prefill(self, merged: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor,
                 grids: Sequence[Tuple[int, int, int]], max_new_tokens: int):
         """score_logits that also keeps the KV cache for `max_new_tokens - 1` further positions.
         -> (fp32 [B, vocab] logits of the last prompt position, state for decode())."""
-        lay = text_layout(self.cfg, input_ids.cpu(), attention_mask.cpu(), grids)
-        with torch.cuda.device(self.device):
-            dev = self.device
-            B, L = input_ids.shape
-            Lmax = L + max(int(max_new_tokens) - 1, 0)
-            ids = input_ids.to(dev, torch.int32).contiguous()
-            t = {k: lay[k].to(dev) for k in ("vis_slot", "seq_len", "last_row", "cos", "sin")}
-            logits = torch.empty(B, self.cfg.text.vocab, dtype=torch.float32, device=dev)
-            self._merged_matches_mode(merged)
-            kv = torch.empty(self.lib.vqs_qwen_kv_bytes(self._h, B, Lmax), dtype=torch.uint8, device=dev)
-            ws = self._workspace(self.lib.vqs_qwen_score_workspace_bytes(self._h, B, L))
-            self._check(self.lib.vqs_qwen_prefill(self._h, merged.contiguous().data_ptr(), ids.data_ptr(), t["vis_slot"].data_ptr(),
-                                                  t["seq_len"].data_ptr(), t["last_row"].data_ptr(), t["cos"].data_ptr(),
-                                                  t["sin"].data_ptr(), B, L, logits.data_ptr(), ws.data_ptr(), ws.numel(), kv.data_ptr(),
-                                                  kv.numel(), Lmax, _stream_ptr()), "vqs_qwen_prefill")
-            # len_host_max: the longest sample's length, tracked on the HOST -- decode() checks the cache bound without reading the device
-            # tensor (round 3 did `int(state["len"].max())` per step: a device sync that serialised the host's ~400 launches per step
-            # with the GPU's work; the decode kernels themselves ignore / clamp a length outside the cache, qwen_decode.hip)
-            # pos: the next token's M-RoPE position per axis, kept ON THE DEVICE -- decode() derives its cos / sin tables there (a few
-            # tiny launches) instead of on the host: the host tables cost two blocking H2D copies per step, each a stream synchronise
-            # (PyTorch syncs after a pageable copy), i.e. the host's launches never overlapped the GPU's work, and torch's CPU thread
-            # pool stalled a step by 70 ms now and then (profiles/r4_call15_*)
-            state = {"kv": kv, "len": t["seq_len"].clone(), "Lmax": Lmax, "B": B, "pos": lay["next_pos"].clone().to(dev), "steps": 0,
-                     "len_host_max": int(lay["seq_len"].max())}
-            return logits, state
+        return self._full_pass(merged, input_ids, attention_mask, grids, max_new_tokens)
 
     def score_shared(self, merged: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor, grids: Sequence[Tuple[int, int, int]],
                      media: Sequence, max_new_tokens: int = 1):
@@ -219,8 +219,8 @@ class QwenEngine:
             merged = merged.contiguous()
             n_vis = merged.shape[0] // B
             merged_u = merged.view(B, n_vis, -1)[plan["first"]].reshape(U * n_vis, -1).contiguous()
-            t = {k: plan[k].to(dev).contiguous() for k in ("media_idx", "prefix_ids", "prefix_vis_slot", "prefix_cos", "prefix_sin", "suffix_ids",
-                                                         "suffix_vis_slot", "suffix_cos", "suffix_sin", "seq_len", "last_row")}
+            t = self._upload(plan, ("media_idx", "prefix_ids", "prefix_vis_slot", "prefix_cos", "prefix_sin", "suffix_ids", "suffix_vis_slot",
+                                    "suffix_cos", "suffix_sin", "seq_len", "last_row"))
             pkv = torch.empty(self.lib.vqs_qwen_prefix_kv_bytes(self._h, U, Lp), dtype=torch.uint8, device=dev)
             ws = self._workspace(max(self.lib.vqs_qwen_prefix_workspace_bytes(self._h, U, Lp), self.lib.vqs_qwen_suffix_workspace_bytes(self._h, B, Lp, Ls)))
             self._check(self.lib.vqs_qwen_prefix(self._h, merged_u.data_ptr(), t["prefix_ids"].data_ptr(), t["prefix_vis_slot"].data_ptr(),
@@ -236,10 +236,7 @@ class QwenEngine:
             Lmax = L + int(max_new_tokens) - 1
             kv = torch.empty(self.lib.vqs_qwen_kv_bytes(self._h, B, Lmax), dtype=torch.uint8, device=dev)
             self._check(self.lib.vqs_qwen_prefill_suffix(*args, kv.data_ptr(), kv.numel(), Lmax, _stream_ptr()), "vqs_qwen_prefill_suffix")
-            # the same decode state as prefill() (see there)
-            state = {"kv": kv, "len": t["seq_len"].clone(), "Lmax": Lmax, "B": B, "pos": plan["next_pos"].clone().to(dev), "steps": 0,
-                     "len_host_max": int(plan["seq_len"].max())}
-            return logits, state
+            return logits, self._decode_state(plan, kv, t["seq_len"], Lmax)
 
     def decode(self, state, token_ids: torch.Tensor) -> torch.Tensor:
         """One further position per sample: token_ids long [B] (the tokens just generated; anything for stopped samples)

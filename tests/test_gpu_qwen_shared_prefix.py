@@ -145,3 +145,53 @@ def test_shared_prefix_7b_two_videos_four_questions_and_the_grid_tool(tmp_path):
     recs = tool.run_grid(m, paths, [1, 4], reps=1)
     assert [r["scores_bitwise_equal"] for r in recs if "scores_bitwise_equal" in r] == [True, True]
     assert all(r["ms_per_grid"] > 0 for r in recs if "ms_per_grid" in r)
+
+
+def test_suffix_pass_rows_are_bitwise_the_full_pass_rows_at_every_tapped_stage():
+    """The one language-model pass (text_pass) taps its intermediates in every mode: for one 4-frame video (64 vision tokens) and five
+    questions, one of them longer than a 128-row attention block, every valid suffix row r - Lp of score_shared's suffix pass is bitwise row r
+    of score_logits' full pass -- the stream and the FFN output at the first and the last layer, and the final stream -- in both forms."""
+    from t2v_metrics_amd.qwen.layout import shared_prefix_plan
+    cfg = get_qwen_config("qwen-tiny")
+    m = _model("qwen-tiny", seed=9)
+    rng = np.random.RandomState(4)
+    px, grid = m.preprocess({"type": "video", "frames": rng.randint(0, 256, (4, 112, 224, 3), dtype=np.uint8)})
+    eng = m.engine
+    TH, last = cfg.text.hidden, cfg.text.layers - 1
+    # in the order the pass produces them; h / h_out are the fp32 stream, d_mlp is a 16-bit tensor (bf16, or fp16 behind its scale)
+    names = [("txt.0.h", 4), ("txt.0.d_mlp", 2), (f"txt.{last}.h", 4), (f"txt.{last}.d_mlp", 2), ("txt.h_out", 4)]
+    try:
+        for f16 in ([True, False] if eng.fp16_active else [False]):
+            eng.set_option("fp16", 1 if f16 else 0)
+            merged1 = eng.encode_vision(px, [grid])
+            assert merged1.shape[0] == 64
+            rows = [m.build_ids(q, "video", 64) for q in QUESTIONS + [LONG]]
+            B, L = len(rows), max(len(r) for r in rows)
+            ids = torch.zeros(B, L, dtype=torch.long)
+            mask = torch.zeros(B, L, dtype=torch.long)
+            for k, r in enumerate(rows):
+                ids[k, : len(r)] = torch.tensor(r)
+                mask[k, : len(r)] = 1
+            merged, grids = torch.cat([merged1] * B), [grid] * B
+            plan = shared_prefix_plan(cfg, ids, mask, grids, [0] * B)
+            assert plan is not None and plan["U"] == 1
+            Lp, Ls, seq_len = plan["Lp"], plan["Ls"], plan["seq_len"].tolist()
+            assert max(seq_len) - Lp > 128, "one suffix must span more than one 128-row attention block"
+            # B * L rows hold the full pass, the prefix pass (Lp rows) and the suffix pass (B * Ls rows)
+            bufs = {n: torch.zeros(B * L * TH * size, dtype=torch.uint8, device="cuda") for n, size in names}
+            for n, _ in names:
+                eng.tap(n, bufs[n])
+            ref = eng.score_logits(merged, ids, mask, grids)
+            full = {n: bufs[n].clone().view(B, L, TH * size) for n, size in names}
+            for n, _ in names:
+                bufs[n].zero_()
+            got, _ = eng.score_shared(merged, ids, mask, grids, [0] * B, 1)
+            for n, size in names:
+                sfx = bufs[n][: B * Ls * TH * size].view(B, Ls, TH * size)
+                for b in range(B):
+                    assert Lp < seq_len[b] <= Lp + Ls
+                    same = torch.equal(sfx[b, : seq_len[b] - Lp], full[n][b, Lp : seq_len[b]])
+                    assert same, f"first difference at tap {n} (fp16 forms {f16}): sample {b}'s suffix rows are not the full pass's"
+            assert torch.equal(got, ref)
+    finally:
+        eng.tap(None)
