@@ -69,6 +69,22 @@ int vqs_debug_qwen_attention_suffix(const void* d_q, const void* d_k, const void
                                     int32_t Hkv, int32_t S, int32_t Sq, int32_t q0, float scale, int32_t f16, void* stream);
 int vqs_debug_qwen_kv_assemble(const void* d_pk, const void* d_pv, const void* d_sk, const void* d_sv, const int32_t* d_media_idx, void* d_dk, void* d_dv,
                                int32_t B, int32_t U, int32_t Hkv, int32_t Lp, int32_t Ls, void* stream);
+/* Single-launch test hooks of the Qwen2.5-VL decode-step kernels (csrc/qwen_decode.hip), on caller tensors; head width 128.
+ *   vqs_debug_qwen_decode_attention: launch_qwen_decode_attn (mode 0) / launch_qwen_tail_attn (modes 1, 2) and nothing else.  kc / vc
+ *     [B, Hkv, Lmax, 128].  mode 0, the decode step: q bf16 [B, Hq * 128], len[b] = the position just appended (keys [0, len[b]]), out bf16
+ *     [B, Hq * 128].  mode 1, the precise tail: q fp32, len[b] = the COUNT of keys, out split-bf16 (hi plane at out, lo plane out_plane elements
+ *     further).  mode 2: mode 1 over IEEE fp16 K / V (the key scale folded into `scale`, the output multiplied by vscale).  A length outside
+ *     the cache is clamped by the kernels (mode 0: to [0, Lmax - 1]; modes 1, 2: to [1, Lmax]).
+ *   vqs_debug_qwen_decode_rope_append: launch_qwen_decode_rope_append: qkv bf16 [B, (Hq + 2 Hkv) * hd], cos / sin fp32 [B, half], q_out
+ *     [B, Hq * hd], kc / vc [B, Hkv, Lmax, hd]; a sample whose len[b] is outside [0, Lmax) writes nothing.
+ *   vqs_debug_qwen_decode_attention_form: host-side, no device access: the kernel the launcher picks for this geometry, by the launcher's own
+ *     function (vqs_kernels.h qwen_decode_attn_form): 1 = the grouped-query kernel, 0 = the per-query-head kernel, -1 = not launchable;
+ *     *lds_bytes (may be NULL) = the launch's dynamic LDS bytes (0 when not launchable). */
+int vqs_debug_qwen_decode_attention(const void* d_q, const void* d_kc, const void* d_vc, const int32_t* d_len, void* d_out, int64_t out_plane, int32_t B,
+                                    int32_t Hq, int32_t Hkv, int32_t Lmax, float scale, float vscale, int32_t mode, void* stream);
+int vqs_debug_qwen_decode_rope_append(const void* d_qkv, const float* d_cos, const float* d_sin, const int32_t* d_len, void* d_q_out, void* d_kc, void* d_vc,
+                                      int32_t B, int32_t Hq, int32_t Hkv, int32_t hd, int32_t half, int32_t Lmax, void* stream);
+int vqs_debug_qwen_decode_attention_form(int32_t Hq, int32_t Hkv, int32_t Lmax, int64_t* lds_bytes);
 /* Tap window: taps copy only the rows of `count` consecutive outer entries starting at `first` -- pairs for the T5 stacks
  * (rows [first*S, (first+count)*S) of an [B*S, W] tensor, the same fraction of a head-major [B, H, S, 64] or a [B*T, W] one),
  * images for the vision tower (so the window's pairs must reference images first .. first+count-1 in order, as the bench

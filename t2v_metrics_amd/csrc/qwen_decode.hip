@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(256) qwen_decode_attn_kernel(const void* __res
 // per lane, summed over the row's 16 lanes by xor-shuffles (1, 2, 4, 8), scaled, kept in LDS [G][Lmax]; softmax statistics per head in
 // fp32, probabilities NOT rounded (as above); output: per lane 8 dims x G heads of fp32 accumulators, the 4 key sub-rows folded by
 // xor-shuffles (16, 32), the four waves' partial rows added in wave order, one division, bf16.  Dynamic LDS: G * Lmax floats.
-static constexpr int QD_GMAX = 8;
+static constexpr int QD_GMAX = QWEN_DECODE_GMAX;
 static constexpr int QD_NW = 8;            // waves per block: eight split the key range, two per SIMD cover each other's load latency
 template <bool PRECISE, bool KVH = false>
 __global__ void __launch_bounds__(64 * QD_NW) qwen_decode_attn_gqa_kernel(const void* __restrict__ q_, const bf16_t* __restrict__ kc,
@@ -359,19 +359,19 @@ template <bool PRECISE, bool KVH = false>
 static hipError_t launch_decode_attn_t(const void* q, const bf16_t* kc, const bf16_t* vc, const int* len, bf16_t* out, int B, int Hq, int Hkv, int Lmax,
                                        float scale, long long out_plane, hipStream_t s, float vscale = 1.0f) {
     if (B <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) != 0 || Lmax <= 0 || Lmax > 36864 /* VQS_QWEN_MAX_CACHE_POSITIONS */ || B > 65535) return hipErrorInvalidValue;
-    {   // grouped-query form wherever its G score rows fit LDS (Lmax <= ~4 300 positions at G = 7); the per-query-head kernel beyond
-        const int G = Hq / Hkv;
-        const size_t glds = (size_t)G * ((Lmax + 3) & ~3) * sizeof(float);
-        if (G <= QD_GMAX && glds <= 120 * 1024) {
-            if (glds > 48 * 1024) {
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(qwen_decode_attn_gqa_kernel<PRECISE, KVH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds);
-                if (e != hipSuccess) return e;
-            }
-            hipLaunchKernelGGL((qwen_decode_attn_gqa_kernel<PRECISE, KVH>), dim3((unsigned)Hkv, (unsigned)B), dim3(64 * QD_NW), glds, s, q, kc, vc, len, out, Hq, Hkv, Lmax, scale, out_plane, vscale);
-            return hipGetLastError();
+    // grouped-query form wherever its G score rows fit LDS (Lmax <= ~4 300 positions at G = 7); the per-query-head kernel beyond
+    // (vqs_kernels.h qwen_decode_attn_form: the decision and the dynamic LDS bytes)
+    size_t lds = 0;
+    const int form = qwen_decode_attn_form(Hq, Hkv, Lmax, &lds);
+    if (form < 0) return hipErrorInvalidValue;
+    if (form == 1) {
+        if (lds > 48 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(qwen_decode_attn_gqa_kernel<PRECISE, KVH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
         }
+        hipLaunchKernelGGL((qwen_decode_attn_gqa_kernel<PRECISE, KVH>), dim3((unsigned)Hkv, (unsigned)B), dim3(64 * QD_NW), lds, s, q, kc, vc, len, out, Hq, Hkv, Lmax, scale, out_plane, vscale);
+        return hipGetLastError();
     }
-    const size_t lds = (size_t)Lmax * sizeof(float);
     if (lds > 48 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(qwen_decode_attn_kernel<PRECISE, KVH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

@@ -1325,6 +1325,30 @@ int vqs_debug_qwen_kv_assemble(const void* pk, const void* pv, const void* sk, c
                                                  (bf16_t*)dv, B, U, Hkv, Lp, Ls, (hipStream_t)stream));
 }
 
+int vqs_debug_qwen_decode_attention(const void* q, const void* kc, const void* vc, const int32_t* len, void* out, int64_t out_plane, int32_t B, int32_t Hq,
+                                    int32_t Hkv, int32_t Lmax, float scale, float vscale, int32_t mode, void* stream) {
+    if (!q || !kc || !vc || !len || !out || mode < 0 || mode > 2) return VQS_ERR_INVALID;
+    if (mode == 0)
+        return vqs::abi_code(vqs::launch_qwen_decode_attn((const bf16_t*)q, (const bf16_t*)kc, (const bf16_t*)vc, len, (bf16_t*)out, B, Hq, Hkv, Lmax, scale,
+                                                          (hipStream_t)stream));
+    return vqs::abi_code(vqs::launch_qwen_tail_attn((const float*)q, (const bf16_t*)kc, (const bf16_t*)vc, len, (bf16_t*)out, (long long)out_plane, B, Hq, Hkv, Lmax,
+                                                    scale, (hipStream_t)stream, mode == 2, mode == 2 ? vscale : 1.0f));
+}
+
+int vqs_debug_qwen_decode_rope_append(const void* qkv, const float* cs, const float* sn, const int32_t* len, void* q_out, void* kc, void* vc, int32_t B,
+                                      int32_t Hq, int32_t Hkv, int32_t hd, int32_t half, int32_t Lmax, void* stream) {
+    if (!qkv || !cs || !sn || !len || !q_out || !kc || !vc) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_qwen_decode_rope_append((const bf16_t*)qkv, cs, sn, len, (bf16_t*)q_out, (bf16_t*)kc, (bf16_t*)vc, B, Hq, Hkv, hd, half, Lmax,
+                                                             (hipStream_t)stream));
+}
+
+int vqs_debug_qwen_decode_attention_form(int32_t Hq, int32_t Hkv, int32_t Lmax, int64_t* lds_bytes) {
+    size_t lds = 0;
+    const int form = vqs::qwen_decode_attn_form(Hq, Hkv, Lmax, &lds);
+    if (lds_bytes) *lds_bytes = (int64_t)lds;
+    return form;
+}
+
 int vqs_debug_norm16(int32_t kind, float* x, const void* delta, const void* delta2, int32_t store_x, const void* w, const void* b,
                      void* out, int32_t M, int32_t D, float eps, int32_t types, void* stream) {
     if (!x || !w || !out || (kind == 1 && !b) || (kind != 0 && kind != 1)) return VQS_ERR_INVALID;

@@ -265,6 +265,20 @@ hipError_t launch_qwen_decode_attn(const bf16_t* q, const bf16_t* kc, const bf16
                                    int Hkv, int Lmax, float scale, hipStream_t s);
 hipError_t launch_qwen_tail_attn(const float* q, const bf16_t* k, const bf16_t* v, const int* count, bf16_t* out, long long out_plane, int B, int Hq,
                                  int Hkv, int Lmax, float scale, hipStream_t s, bool kv_f16 = false, float vscale = 1.0f);
+// Which kernel a launch_qwen_decode_attn / launch_qwen_tail_attn call takes (host arithmetic; the launcher and the test hook
+// vqs_debug_qwen_decode_attention_form share it): 1 = the grouped-query kernel (one block per key/value head, G = Hq / Hkv <= 8 rows of
+// ((Lmax + 3) & ~3) fp32 scores in dynamic LDS, up to 120 KiB), 0 = the per-query-head kernel (Lmax fp32 scores), -1 = not launchable.
+// *lds_bytes = the launch's dynamic LDS (above 48 KiB the launcher raises the kernel's limit with hipFuncSetAttribute first).
+constexpr int QWEN_DECODE_GMAX = 8;
+inline int qwen_decode_attn_form(int Hq, int Hkv, int Lmax, size_t* lds_bytes) {
+    if (lds_bytes) *lds_bytes = 0;
+    if (Hq <= 0 || Hkv <= 0 || (Hq % Hkv) != 0 || Lmax <= 0 || Lmax > 36864 /* VQS_QWEN_MAX_CACHE_POSITIONS */) return -1;
+    const int G = Hq / Hkv;
+    const size_t glds = (size_t)G * ((Lmax + 3) & ~3) * sizeof(float);
+    const bool grouped = G <= QWEN_DECODE_GMAX && glds <= 120 * 1024;
+    if (lds_bytes) *lds_bytes = grouped ? glds : (size_t)Lmax * sizeof(float);
+    return grouped ? 1 : 0;
+}
 // bind-time range proof of the Qwen2.5-VL row's fp16 forms (qwen_decode.hip): per-row bounds of a linear's output, their maximum into `slot`
 hipError_t launch_rowbound(const bf16_t* W, long long ldw, int N, int K, int mode, const bf16_t* g, int g_len, float R, const float* u,
                            const float* uconst, const bf16_t* bias, float* out, float* slot, hipStream_t s);

@@ -77,6 +77,9 @@ _SIGNATURES = {
     "vqs_debug_qwen_attention": (_c_i32, [_c_vp] * 5 + [_c_i32] * 4 + [ctypes.c_float, _c_i32, _c_vp]),
     "vqs_debug_qwen_attention_suffix": (_c_i32, [_c_vp] * 5 + [_c_i32] * 6 + [ctypes.c_float, _c_i32, _c_vp]),
     "vqs_debug_qwen_kv_assemble": (_c_i32, [_c_vp] * 7 + [_c_i32] * 5 + [_c_vp]),
+    "vqs_debug_qwen_decode_attention": (_c_i32, [_c_vp] * 5 + [_c_i64] + [_c_i32] * 4 + [ctypes.c_float, ctypes.c_float, _c_i32, _c_vp]),
+    "vqs_debug_qwen_decode_rope_append": (_c_i32, [_c_vp] * 7 + [_c_i32] * 6 + [_c_vp]),
+    "vqs_debug_qwen_decode_attention_form": (_c_i32, [_c_i32] * 3 + [ctypes.POINTER(_c_i64)]),
     "vqs_debug_norm16": (_c_i32, [_c_i32, _c_vp, _c_vp, _c_vp, _c_i32, _c_vp, _c_vp, _c_vp, _c_i32, _c_i32, ctypes.c_float, _c_i32, _c_vp]),
     "vqs_debug_gemm_form": (_c_i32, [_c_i32] * 11),
     "vqs_debug_gemm_batched": (_c_i32, [_c_vp, _c_vp, _c_vp] + [_c_i32] * 8 + [_c_i64] * 4 + [_c_i32, _c_i32, _c_vp]),
