@@ -176,6 +176,10 @@ int vqs_rope(void* d_x, const float* d_cos, const float* d_sin, int32_t B, int32
  * q [B,H,S,hd], k/v [B,Hkv,S,hd] bf16 head-major; out bf16 [B*S, H*hd]; key_len [B] or NULL. */
 int vqs_attention_hd(const void* d_q, const void* d_k, const void* d_v, void* d_out, const int32_t* d_key_len, int32_t B,
                      int32_t H, int32_t Hkv, int32_t S, int32_t hd, float scale, int32_t causal, void* stream);
+/* Decoder attention, T <= 16 query rows per sample (self: causal + bias table [H, T]; cross: k / v [B,H,S,64] head-major, key_len [B]).
+ * Cross form preconditions: key_len[b] >= 1 (with no key every score is masked alike and the output is the plain mean of all S value rows,
+ * not zeros), and the VALUE rows at positions >= key_len[b] must be finite -- they are multiplied by a probability of exactly 0, and
+ * 0 * NaN is NaN (the engine's encoder rows past a prompt's length are zeros); the key rows there are masked whatever they hold. */
 int vqs_decoder_attention(const void* d_q, const void* d_k, const void* d_v, void* d_out, const float* d_bias_table,
                           const int32_t* d_key_len, int32_t B, int32_t H, int32_t T, int32_t S, int32_t ldq, int32_t ldk,
                           int32_t cross, void* stream);

@@ -85,6 +85,48 @@ int vqs_debug_qwen_decode_attention(const void* d_q, const void* d_kc, const voi
 int vqs_debug_qwen_decode_rope_append(const void* d_qkv, const float* d_cos, const float* d_sin, const int32_t* d_len, void* d_q_out, void* d_kc, void* d_vc,
                                       int32_t B, int32_t Hq, int32_t Hkv, int32_t hd, int32_t half, int32_t Lmax, void* stream);
 int vqs_debug_qwen_decode_attention_form(int32_t Hq, int32_t Hkv, int32_t Lmax, int64_t* lds_bytes);
+/* Single-launch test hooks of the precise decoder's glue, the split-K reductions and the greedy / score tail (csrc/elementwise.hip,
+ * csrc/attn.hip), on caller tensors: each calls ONE launcher with the caller's arguments and nothing else (no copy, no synchronisation); a
+ * launcher's refusal (a shape or an alignment it does not take) comes back as VQS_ERR_INVALID and nothing is launched.
+ *   vqs_debug_rmsnorm_split: launch_rmsnorm_split: x fp32 [M, D] (+= delta fp32 [M, D] when not NULL, written back), w bf16 [D], out split-bf16:
+ *     hi plane [M, D] at out, lo plane out_plane elements further.  D % 4 == 0, out_plane % 4 == 0.
+ *   vqs_debug_sum_planes: launch_sum_planes: part fp32 [nslices][2 rows][ldp] (slice k at part + k slice_stride; hi rows, then lo rows),
+ *     mode 0: out fp32 [rows, ld_out]; 1: split-bf16 planes [rows, ld_out] at out and out + out_plane; 2: cols = 2 F packed gate | linear
+ *     columns (blocks of 64 = 32 | 32) -> split(act(gate) * linear), F columns; 3: IEEE fp16 [rows, ld_out].  bias (bf16 [cols], may be NULL)
+ *     and silu != 0 select the Qwen2.5-VL tail's forms (bias added to the sums; the gate's activation is SiLU instead of gelu_new); mode 3
+ *     has no such form.
+ *   vqs_debug_reduce_slices: launch_reduce_slices: out bf16 [n] = sum over slices of part fp32 [nslices][n], in index order; n % 4 == 0.
+ *   vqs_debug_reduce_slices_act: launch_reduce_slices_act: out bf16 [rows, ld_out] = f(sum over slices of part [nslices][rows][ldp] (+ bias));
+ *     gated != 0: packed gate | up columns -> SiLU(gate) * up, cols / 2 columns.
+ *   vqs_debug_masked_softmax: launch_masked_softmax: scores fp32 [B * rows, S_pad] -> probs [B * rows, S_pad] (bf16, or IEEE fp16 when
+ *     out_f16 != 0), 0 for keys >= min(key_len[b], S_pad).
+ *   vqs_debug_transpose_pad: launch_transpose_pad: in bf16 [B, S, D] -> out [B, D, S_pad], columns >= S zero.  D % 64 == 0, S_pad % 64 == 0.
+ *   vqs_debug_argmax_append: launch_argmax_append: tokens[b, dst_col] (dst_col < 0: T - 1) = argmax of logits row b T + T - 1 over [0, V), the
+ *     lowest index on ties; flags (may be NULL): bit 1 is set when a scanned logit is not finite.
+ *   vqs_debug_decoder_attention: launch_decoder_attention with every field of its parameter block: vqs_decoder_attention plus the cached
+ *     self form (qpos0 = decoder position of query row 0, S = qpos0 + T keys, kv_stride_b elements between the samples' K / V rows, bias_ld =
+ *     row length of the bias table; 0 = the teacher-forced defaults) and the precise self form (precise != 0: q / k / v fp32 [B T, ldq], the
+ *     output split-bf16 with the lo plane out_plane elements after the hi plane).  Cross form: keys at positions >= key_len[b] are masked
+ *     whatever they hold; value rows there are multiplied by a probability of exactly 0 and must be finite (vqs_decoder_attention, vqs.h).
+ *   vqs_debug_score_head: launch_score_head (vqs_score_head of vqs.h) with the pass's status word: flags (may be NULL) bit 1 is set when a
+ *     sample's summed label log-probs are not finite. */
+int vqs_debug_rmsnorm_split(float* d_x, const float* d_delta, const void* d_w, void* d_out, int64_t out_plane, int32_t M, int32_t D, float eps,
+                            void* stream);
+int vqs_debug_sum_planes(const float* d_part, int32_t nslices, int64_t slice_stride, int32_t rows, int32_t cols, int32_t ldp, int32_t mode, void* d_out,
+                         int32_t ld_out, int64_t out_plane, const void* d_bias, int32_t silu, void* stream);
+int vqs_debug_reduce_slices(const float* d_part, int32_t nslices, int64_t n, void* d_out, void* stream);
+int vqs_debug_reduce_slices_act(const float* d_part, int32_t nslices, int64_t slice_stride, int32_t rows, int32_t cols, int32_t ldp, const void* d_bias,
+                                int32_t gated, void* d_out, int32_t ld_out, void* stream);
+int vqs_debug_masked_softmax(const float* d_scores, void* d_probs, const int32_t* d_key_len, int32_t B, int32_t rows, int32_t S_pad, int32_t out_f16,
+                             void* stream);
+int vqs_debug_transpose_pad(const void* d_in, void* d_out, int32_t B, int32_t S, int32_t D, int32_t S_pad, void* stream);
+int vqs_debug_argmax_append(const float* d_logits, int32_t ldl, int32_t V, int32_t* d_tokens, int32_t ld_tokens, int32_t B, int32_t T, int32_t dst_col,
+                            int32_t* d_flags, void* stream);
+int vqs_debug_decoder_attention(const void* d_q, const void* d_k, const void* d_v, void* d_out, const float* d_bias_table, const int32_t* d_key_len,
+                                int32_t B, int32_t H, int32_t T, int32_t S, int32_t ldq, int32_t ldk, int32_t cross, int64_t kv_stride_b, int32_t qpos0,
+                                int32_t bias_ld, int32_t precise, int64_t out_plane, void* stream);
+int vqs_debug_score_head(const float* d_logits, int32_t ldl, int32_t V, const int32_t* d_labels, float* d_lp, float* d_scores, int32_t B, int32_t T,
+                         int32_t* d_flags, void* stream);
 /* Tap window: taps copy only the rows of `count` consecutive outer entries starting at `first` -- pairs for the T5 stacks
  * (rows [first*S, (first+count)*S) of an [B*S, W] tensor, the same fraction of a head-major [B, H, S, 64] or a [B*T, W] one),
  * images for the vision tower (so the window's pairs must reference images first .. first+count-1 in order, as the bench

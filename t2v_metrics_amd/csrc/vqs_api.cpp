@@ -1349,6 +1349,63 @@ int vqs_debug_qwen_decode_attention_form(int32_t Hq, int32_t Hkv, int32_t Lmax, 
     return form;
 }
 
+// ---- single-launch hooks of the precise decoder's glue, the split-K reductions and the greedy / score tail (include/vqs_debug.h)
+int vqs_debug_rmsnorm_split(float* x, const float* delta, const void* w, void* out, int64_t out_plane, int32_t M, int32_t D, float eps, void* stream) {
+    if (!x || !w || !out) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_rmsnorm_split(x, delta, (const bf16_t*)w, (bf16_t*)out, (long long)out_plane, M, D, eps, (hipStream_t)stream));
+}
+
+int vqs_debug_sum_planes(const float* part, int32_t nslices, int64_t slice_stride, int32_t rows, int32_t cols, int32_t ldp, int32_t mode, void* out,
+                         int32_t ld_out, int64_t out_plane, const void* bias, int32_t silu, void* stream) {
+    if (!part || !out) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_sum_planes(part, nslices, (long long)slice_stride, rows, cols, ldp, mode, out, ld_out, (long long)out_plane,
+                                                (hipStream_t)stream, (const bf16_t*)bias, silu));
+}
+
+int vqs_debug_reduce_slices(const float* part, int32_t nslices, int64_t n, void* out, void* stream) {
+    if (!part || !out || nslices <= 0 || n <= 0) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_reduce_slices(part, nslices, (size_t)n, (bf16_t*)out, (hipStream_t)stream));
+}
+
+int vqs_debug_reduce_slices_act(const float* part, int32_t nslices, int64_t slice_stride, int32_t rows, int32_t cols, int32_t ldp, const void* bias,
+                                int32_t gated, void* out, int32_t ld_out, void* stream) {
+    if (!part || !out) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_reduce_slices_act(part, nslices, (long long)slice_stride, rows, cols, ldp, (const bf16_t*)bias, gated, (bf16_t*)out,
+                                                       ld_out, (hipStream_t)stream));
+}
+
+int vqs_debug_masked_softmax(const float* scores, void* probs, const int32_t* key_len, int32_t B, int32_t rows, int32_t S_pad, int32_t out_f16,
+                             void* stream) {
+    if (!scores || !probs || !key_len || B <= 0 || rows <= 0 || S_pad <= 0) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_masked_softmax(scores, (bf16_t*)probs, key_len, B, rows, S_pad, (hipStream_t)stream, out_f16 != 0));
+}
+
+int vqs_debug_transpose_pad(const void* in, void* out, int32_t B, int32_t S, int32_t D, int32_t S_pad, void* stream) {
+    if (!in || !out || B <= 0 || S <= 0 || D <= 0) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_transpose_pad((const bf16_t*)in, (bf16_t*)out, B, S, D, S_pad, (hipStream_t)stream));
+}
+
+int vqs_debug_argmax_append(const float* logits, int32_t ldl, int32_t V, int32_t* tokens, int32_t ld_tokens, int32_t B, int32_t T, int32_t dst_col,
+                            int32_t* flags, void* stream) {
+    if (!logits || !tokens || B <= 0 || T <= 0 || V <= 0) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_argmax_append(logits, ldl, V, tokens, ld_tokens, B, T, (hipStream_t)stream, dst_col, flags));
+}
+
+int vqs_debug_decoder_attention(const void* q, const void* k, const void* v, void* out, const float* bias_table, const int32_t* key_len, int32_t B,
+                                int32_t H, int32_t T, int32_t S, int32_t ldq, int32_t ldk, int32_t cross, int64_t kv_stride_b, int32_t qpos0,
+                                int32_t bias_ld, int32_t precise, int64_t out_plane, void* stream) {
+    if (!q || !k || !v || !out || B <= 0 || H <= 0) return VQS_ERR_INVALID;
+    vqs::DecAttnParams a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, bias_table, key_len, B, H, T, S, ldq, ldk, cross};
+    a.kv_stride_b = (long long)kv_stride_b; a.qpos0 = qpos0; a.bias_ld = bias_ld; a.precise = precise; a.out_plane = (long long)out_plane;
+    return vqs::abi_code(vqs::launch_decoder_attention(a, (hipStream_t)stream));
+}
+
+int vqs_debug_score_head(const float* logits, int32_t ldl, int32_t V, const int32_t* labels, float* lp, float* scores, int32_t B, int32_t T,
+                         int32_t* flags, void* stream) {
+    if (!logits || !labels || !lp || !scores || B <= 0 || T <= 0 || V <= 0) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_score_head(logits, ldl, V, labels, lp, scores, B, T, (hipStream_t)stream, flags));
+}
+
 int vqs_debug_norm16(int32_t kind, float* x, const void* delta, const void* delta2, int32_t store_x, const void* w, const void* b,
                      void* out, int32_t M, int32_t D, float eps, int32_t types, void* stream) {
     if (!x || !w || !out || (kind == 1 && !b) || (kind != 0 && kind != 1)) return VQS_ERR_INVALID;

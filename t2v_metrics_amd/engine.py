@@ -80,6 +80,15 @@ _SIGNATURES = {
     "vqs_debug_qwen_decode_attention": (_c_i32, [_c_vp] * 5 + [_c_i64] + [_c_i32] * 4 + [ctypes.c_float, ctypes.c_float, _c_i32, _c_vp]),
     "vqs_debug_qwen_decode_rope_append": (_c_i32, [_c_vp] * 7 + [_c_i32] * 6 + [_c_vp]),
     "vqs_debug_qwen_decode_attention_form": (_c_i32, [_c_i32] * 3 + [ctypes.POINTER(_c_i64)]),
+    "vqs_debug_rmsnorm_split": (_c_i32, [_c_vp] * 4 + [_c_i64, _c_i32, _c_i32, ctypes.c_float, _c_vp]),
+    "vqs_debug_sum_planes": (_c_i32, [_c_vp, _c_i32, _c_i64] + [_c_i32] * 4 + [_c_vp, _c_i32, _c_i64, _c_vp, _c_i32, _c_vp]),
+    "vqs_debug_reduce_slices": (_c_i32, [_c_vp, _c_i32, _c_i64, _c_vp, _c_vp]),
+    "vqs_debug_reduce_slices_act": (_c_i32, [_c_vp, _c_i32, _c_i64] + [_c_i32] * 3 + [_c_vp, _c_i32, _c_vp, _c_i32, _c_vp]),
+    "vqs_debug_masked_softmax": (_c_i32, [_c_vp] * 3 + [_c_i32] * 4 + [_c_vp]),
+    "vqs_debug_transpose_pad": (_c_i32, [_c_vp, _c_vp] + [_c_i32] * 4 + [_c_vp]),
+    "vqs_debug_argmax_append": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_vp] + [_c_i32] * 4 + [_c_vp, _c_vp]),
+    "vqs_debug_decoder_attention": (_c_i32, [_c_vp] * 6 + [_c_i32] * 7 + [_c_i64, _c_i32, _c_i32, _c_i32, _c_i64, _c_vp]),
+    "vqs_debug_score_head": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_vp, _c_vp, _c_vp, _c_i32, _c_i32, _c_vp, _c_vp]),
     "vqs_debug_norm16": (_c_i32, [_c_i32, _c_vp, _c_vp, _c_vp, _c_i32, _c_vp, _c_vp, _c_vp, _c_i32, _c_i32, ctypes.c_float, _c_i32, _c_vp]),
     "vqs_debug_gemm_form": (_c_i32, [_c_i32] * 11),
     "vqs_debug_gemm_batched": (_c_i32, [_c_vp, _c_vp, _c_vp] + [_c_i32] * 8 + [_c_i64] * 4 + [_c_i32, _c_i32, _c_vp]),
@@ -722,14 +731,21 @@ def norm_deferred(x, w, eps, delta, delta2=None, store_x=True, b=None):
     return out
 
 
-def score_head(logits, labels):
+def score_head(logits, labels, V=None, flags=None):
+    """logits fp32 [B, T, ldl] -> (label log-probs [B, T], scores [B]) over the first V columns (default: all of them).  flags: an int32
+    device word, the pass's status word (bit 1 is set when a sample's label log-probs are not finite); it goes through the test hook, since
+    vqs_score_head of include/vqs.h carries none."""
     lib = load_library()
-    B, T, V = logits.shape
+    B, T, ldl = logits.shape
+    V = ldl if V is None else V
     lg = logits.contiguous()
     lab = labels.to(torch.int32).contiguous()
     lp = torch.empty(B, T, dtype=torch.float32, device=logits.device)
     sc = torch.empty(B, dtype=torch.float32, device=logits.device)
-    rc = lib.vqs_score_head(lg.data_ptr(), V, V, lab.data_ptr(), lp.data_ptr(), sc.data_ptr(), B, T, _stream_ptr())
+    if flags is None:
+        rc = lib.vqs_score_head(lg.data_ptr(), ldl, V, lab.data_ptr(), lp.data_ptr(), sc.data_ptr(), B, T, _stream_ptr())
+    else:
+        rc = lib.vqs_debug_score_head(lg.data_ptr(), ldl, V, lab.data_ptr(), lp.data_ptr(), sc.data_ptr(), B, T, flags.data_ptr(), _stream_ptr())
     if rc != 0:
         raise VqsError(f"vqs_score_head failed ({rc})")
     return lp, sc
