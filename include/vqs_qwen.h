@@ -87,6 +87,31 @@ int vqs_qwen_encode_vision(vqs_qwen_handle* h, const void* d_patches, int32_t N,
                            const float* d_sin_w, const float* d_cos_f, const float* d_sin_f, int32_t Np, int32_t win_len,
                            int32_t frame_len, void* d_merged, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Media front end on the device: decoded uint8 frames -> the bf16 patch rows vqs_qwen_encode_vision reads.  Replaces the host lines
+ * between the decoded frames and the tower -- t2v_metrics_amd/models/vqascore_models/qwen25vl_model.py `preprocess` (Pillow
+ * Image.resize(BICUBIC) per frame, x * (1/255), (x - mean) / std in fp32) and `patchify` (HF Qwen2VLVideoProcessor.patchify), and the
+ * .to(bfloat16) of the upload -- BIT FOR BIT: Pillow's 8-bit resampler is integer arithmetic over per-axis tables, which the caller
+ * builds exactly as Pillow does (t2v_metrics_amd/qwen/media.py pillow_bicubic_tables), and the normalisation of a uint8 is a table of
+ * 3 x 256 bf16 values the caller evaluates with the processor's own fp32 expression (normalize_lut).  n media that share source size,
+ * frame count and target size go in one call: at most two launches (horizontal pass; vertical pass + lookup + flatten), no fp32 image.
+ * A free function like vqs_normalize_u8: no handle, no allocation, no synchronisation.
+ *   d_frames     u8 [n, T, H, W, 3]
+ *   rh, rw       size after the resize, multiples of patch * merge (smart_resize); (rh, rw) == (H, W): no resize
+ *   d_x0_h / d_k_h   int32 [rw] first source column and int32 [rw, taps_h] weights (22-bit fixed point, rows zero-padded to taps_h) of every
+ *                output column; NULL / 0 when rw == W.  d_x0_v / d_k_v / taps_v: the same over rows, [rh] and [rh, taps_v]; NULL / 0 when rh == H.
+ *                taps grows with the downscale factor (2 * ceil(2 * max(in / out, 1)) + 1 at most); taps are clamped to the axis on the device.
+ *   d_lut        bf16 [3, 256]: channel c's normalised value of the uint8 v at [c, v]
+ *   d_patches    bf16 [n * t * (rh / patch) * (rw / patch), 3 * temporal * patch * patch] out, t = ceil(T / temporal): HF processor order (the
+ *                last frame repeated to a multiple of `temporal`, rows block-major over merge x merge cells, features [C, Tp, P, P])
+ *   d_ws         vqs_qwen_media_workspace_bytes(...): the horizontal pass's uint8 intermediate; read only when rw != W (the query returns
+ *                256 when there is none, and 0 for sizes that are not positive)
+ * VQS_ERR_INVALID (sizes not positive, rh or rw not a multiple of patch * merge, a table missing where the size changes) and VQS_ERR_WORKSPACE
+ * are returned before any launch. */
+size_t vqs_qwen_media_workspace_bytes(int32_t n, int32_t T, int32_t H, int32_t W, int32_t rh, int32_t rw);
+int vqs_qwen_patches_u8(const void* d_frames, int32_t n, int32_t T, int32_t H, int32_t W, int32_t rh, int32_t rw, const int32_t* d_x0_h,
+                        const int32_t* d_k_h, int32_t taps_h, const int32_t* d_x0_v, const int32_t* d_k_v, int32_t taps_v, const void* d_lut,
+                        int32_t patch, int32_t merge, int32_t temporal, void* d_patches, void* d_ws, size_t ws_bytes, void* stream);
+
 /* Language-model prefill + last-position logits.
  *   d_input_ids  int32 [B, L] right-padded          d_vis_slot int32 [B, L]: row of d_merged for placeholder tokens, else -1
  *   d_seq_len    int32 [B]                           d_last_row int32 [B] = b*L + seq_len[b] - 1

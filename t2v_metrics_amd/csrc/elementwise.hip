@@ -1264,4 +1264,124 @@ hipError_t launch_u8_to_norm_bf16(const unsigned char* in, bf16_t* out, int N, i
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Media front end of the Qwen2.5-VL row (include/vqs_qwen.h vqs_qwen_patches_u8): decoded uint8 frames -> the bf16 patch rows the tower
+// reads, bit for bit what the host path computes (qwen25vl_model.py preprocess + patchify: Pillow's 8-bit bicubic resize per frame,
+// ((x * 1/255) - mean) / std in fp32, bf16, HF's flat patch order).  Pillow's 8-bit resampler is integer arithmetic -- a horizontal pass,
+// then a vertical pass, each clip8(((1 << 21) + sum k_i * px_i) >> 22) over per-axis tables of first taps and 22-bit fixed-point weights
+// that the HOST builds exactly as Pillow does (qwen/media.py); the normalisation of a uint8 is a 3 x 256 bf16 table the host evaluates
+// with the processor's own expression.  So the device only multiplies, adds, shifts and looks up.  The sums fit int32: the weights of one
+// output sum to 2^22 and the bicubic's negative lobes keep sum |k| below 1.3 * 2^22, times 255.  Every tap index is clamped to its axis
+// (the host pads the weight rows with zeros up to `taps`), so no table can steer a read outside the frame.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned char clip8_q22(int acc) {
+    return (unsigned char)min(max(acc >> 22, 0), 255);
+}
+
+// horizontal pass: in u8 [rows, W, 3] -> out u8 [rows, rw, 3] (rows = frames * H); one thread per output pixel
+__global__ void __launch_bounds__(256) qwen_resize_h_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
+                                                            const int* __restrict__ x0, const int* __restrict__ k, int taps,
+                                                            long long rows, int W, int rw) {
+    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= rows * rw) return;
+    const long long row = id / rw;
+    const int x = (int)(id - row * rw);
+    const unsigned char* src = in + (size_t)row * W * 3;
+    const int* kk = k + (size_t)x * taps;
+    const int first = min(max(x0[x], 0), W - 1);
+    int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+    for (int i = 0; i < taps; ++i) {
+        const unsigned char* p = src + (size_t)min(first + i, W - 1) * 3;
+        const int w = kk[i];
+        a0 += w * (int)p[0];
+        a1 += w * (int)p[1];
+        a2 += w * (int)p[2];
+    }
+    unsigned char* o = out + (size_t)id * 3;
+    o[0] = clip8_q22(a0);
+    o[1] = clip8_q22(a1);
+    o[2] = clip8_q22(a2);
+}
+hipError_t launch_qwen_resize_h(const unsigned char* in, unsigned char* out, const int* x0, const int* k, int taps, long long rows, int W,
+                                int rw, hipStream_t s) {
+    const long long blocks = (rows * rw + 255) / 256;
+    if (rows <= 0 || W <= 0 || rw <= 0 || taps <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(qwen_resize_h_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, out, x0, k, taps, rows, W, rw);
+    return hipGetLastError();
+}
+
+// vertical pass (VERT; else the source already has rh rows) + table lookup + HF's patch flatten: src u8 [n * T, Hs, rw, 3] ->
+// out bf16 [n * t * gh * gw, D], D = 3 * temporal * patch * patch.  Row order: medium, temporal patch, then block-major over merge x merge
+// cells; features [C, Tp, P, P]; the last frame stands in for the frames an odd T lacks.  One thread per VEC consecutive features of a row.
+template <bool VERT, int VEC>
+__global__ void __launch_bounds__(256) qwen_patch_rows_kernel(QwenPatchRows p) {
+    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int units = p.D / VEC;
+    if (id >= p.rows * units) return;
+    const long long row = id / units;
+    const int u = (int)(id - row * units);
+    const int per_medium = p.t * p.gh * p.gw;
+    const long long m = row / per_medium;
+    int rr = (int)(row - m * per_medium);
+    const int mw = rr % p.merge; rr /= p.merge;
+    const int mh = rr % p.merge; rr /= p.merge;
+    const int wb = rr % (p.gw / p.merge); rr /= (p.gw / p.merge);
+    const int hb = rr % (p.gh / p.merge);
+    const int tt = rr / (p.gh / p.merge);
+    const int y_base = (hb * p.merge + mh) * p.patch, x_base = (wb * p.merge + mw) * p.patch;
+    const size_t frame_px = (size_t)p.Hs * p.rw;
+    bf16_t v[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        int j = u * VEC + e;
+        const int px = j % p.patch; j /= p.patch;
+        const int py = j % p.patch; j /= p.patch;
+        const int tp = j % p.temporal;
+        const int c = j / p.temporal;
+        const int f = min(tt * p.temporal + tp, p.T - 1);
+        const int y = y_base + py, x = x_base + px;
+        const unsigned char* col = p.src + (((size_t)m * p.T + f) * frame_px + x) * 3 + c;      // (row 0, x, c) of the frame
+        int val;
+        if (VERT) {
+            const int* kk = p.k + (size_t)y * p.taps;
+            const int first = min(max(p.y0[y], 0), p.Hs - 1);
+            int acc = 1 << 21;
+            for (int i = 0; i < p.taps; ++i) acc += kk[i] * (int)col[(size_t)min(first + i, p.Hs - 1) * p.rw * 3];
+            val = clip8_q22(acc);
+        } else {
+            val = col[(size_t)y * p.rw * 3];
+        }
+        v[e] = p.lut[c * 256 + val];
+    }
+    bf16_t* o = p.out + (size_t)row * p.D + (size_t)u * VEC;
+    if (VEC == 4) {
+        uint2 w;
+        w.x = (uint32_t)v[0] | ((uint32_t)v[1 % VEC] << 16);
+        w.y = (uint32_t)v[2 % VEC] | ((uint32_t)v[3 % VEC] << 16);
+        *reinterpret_cast<uint2*>(o) = w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) o[e] = v[e];
+    }
+}
+hipError_t launch_qwen_patch_rows(const QwenPatchRows& p, hipStream_t s) {
+    if (p.rows <= 0 || p.D <= 0 || p.T <= 0 || p.Hs <= 0 || p.rw <= 0 || p.patch <= 0 || p.merge <= 0 || p.temporal <= 0 || p.t <= 0 ||
+        p.gh <= 0 || p.gw <= 0 || p.gh % p.merge || p.gw % p.merge || p.D != 3 * p.temporal * p.patch * p.patch || p.rw != p.gw * p.patch ||
+        (p.k ? (p.taps <= 0 || !p.y0) : p.Hs != p.gh * p.patch) || !p.src || !p.lut || !p.out)
+        return hipErrorInvalidValue;
+    // 8-byte stores of four features where the rows allow them (D = 1176 does)
+    const bool vec4 = p.D % 4 == 0 && ((uintptr_t)p.out & 7) == 0;
+    const long long blocks = (p.rows * (p.D / (vec4 ? 4 : 1)) + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(256);
+    if (p.k) {
+        if (vec4) hipLaunchKernelGGL((qwen_patch_rows_kernel<true, 4>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((qwen_patch_rows_kernel<true, 1>), grid, block, 0, s, p);
+    } else {
+        if (vec4) hipLaunchKernelGGL((qwen_patch_rows_kernel<false, 4>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((qwen_patch_rows_kernel<false, 1>), grid, block, 0, s, p);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace vqs

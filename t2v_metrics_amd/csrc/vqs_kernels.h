@@ -338,6 +338,21 @@ hipError_t launch_qwen_embed(const int* ids, const int* vis_slot, const bf16_t* 
                              int D, int vocab, hipStream_t s, bool merged_f16 = false, float merged_unscale = 1.0f);
 hipError_t launch_u8_to_norm_bf16(const unsigned char* in, bf16_t* out, int N, int H, int W, const float* mean3,
                                   const float* std3, hipStream_t s);
+// ---- media front end of the Qwen2.5-VL row (elementwise.hip; include/vqs_qwen.h vqs_qwen_patches_u8): Pillow's 8-bit bicubic passes over
+// host-built tables (first tap + 22-bit fixed-point weights per output index, weight rows zero-padded to `taps`), then lookup + flatten
+hipError_t launch_qwen_resize_h(const unsigned char* in, unsigned char* out, const int* x0, const int* k, int taps, long long rows, int W,
+                                int rw, hipStream_t s);      // u8 [rows, W, 3] -> u8 [rows, rw, 3]
+struct QwenPatchRows {
+    const unsigned char* src;   // u8 [n * T, Hs, rw, 3]
+    const int* y0;              // vertical tables [gh * patch], [gh * patch, taps]; k == nullptr: no vertical pass (Hs == gh * patch)
+    const int* k;
+    int taps;
+    const bf16_t* lut;          // bf16 [3, 256]: the normalised value of every uint8, per channel
+    bf16_t* out;                // bf16 [rows, D]
+    long long rows;             // n * t * gh * gw
+    int T, Hs, rw, patch, merge, temporal, t, gh, gw, D;
+};
+hipError_t launch_qwen_patch_rows(const QwenPatchRows& p, hipStream_t s);
 hipError_t launch_interleave_gate(const bf16_t* wi0, const bf16_t* wi1, bf16_t* dst, int F, int D, hipStream_t s);
 
 // ---- shared-prompt-prefix passes of the Qwen2.5-VL row (include/vqs_qwen.h vqs_qwen_prefix / vqs_qwen_score_suffix)

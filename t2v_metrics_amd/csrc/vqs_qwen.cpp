@@ -1343,3 +1343,63 @@ int vqs_qwen_prefill_suffix(vqs_qwen_handle* h, const void* d_merged, const int3
 }
 
 }  // extern "C"
+
+// ---- media front end (free functions, no handle): uint8 frames -> the bf16 patch rows of vqs_qwen_encode_vision
+namespace {
+// sizes of one vqs_qwen_patches_u8 call; ok == false: VQS_ERR_INVALID
+struct MediaShape {
+    bool ok = false;
+    int t = 0, gh = 0, gw = 0;
+    long long rows = 0;          // patch rows out
+    size_t h_bytes = 0;          // the horizontal pass's uint8 intermediate [n * T, H, rw, 3]; 0: no horizontal pass
+};
+MediaShape media_shape(int32_t n, int32_t T, int32_t H, int32_t W, int32_t rh, int32_t rw, int32_t patch, int32_t merge, int32_t temporal) {
+    MediaShape m;
+    if (n <= 0 || T <= 0 || H <= 0 || W <= 0 || rh <= 0 || rw <= 0 || patch <= 0 || merge <= 0 || temporal <= 0) return m;
+    const long long cell = (long long)patch * merge;
+    if (cell > 0x7fff || rh % cell || rw % cell) return m;
+    m.t = (T + temporal - 1) / temporal;
+    m.gh = rh / patch;
+    m.gw = rw / patch;
+    m.rows = (long long)n * m.t * m.gh * m.gw;
+    const long long D = 3LL * temporal * patch * patch;
+    // element counts the kernels index with 64 bits but launch with 32-bit grids
+    const long long frames = (long long)n * T;
+    if (D > 0x7fffffffLL || m.rows > (1LL << 40) / D || frames > (1LL << 40) / ((long long)H * W) || frames > (1LL << 40) / ((long long)H * rw) ||
+        (long long)m.t * m.gh * m.gw > 0x7fffffffLL)
+        return m;
+    m.h_bytes = rw != W ? (size_t)frames * H * rw * 3 : 0;
+    m.ok = true;
+    return m;
+}
+}  // namespace
+
+extern "C" {
+
+size_t vqs_qwen_media_workspace_bytes(int32_t n, int32_t T, int32_t H, int32_t W, int32_t rh, int32_t rw) {
+    const MediaShape m = media_shape(n, T, H, W, rh, rw, 1, 1, 1);
+    return m.ok ? std::max<size_t>(align_up(m.h_bytes, 256), 256) : 0;
+}
+
+int vqs_qwen_patches_u8(const void* d_frames, int32_t n, int32_t T, int32_t H, int32_t W, int32_t rh, int32_t rw, const int32_t* d_x0_h,
+                        const int32_t* d_k_h, int32_t taps_h, const int32_t* d_x0_v, const int32_t* d_k_v, int32_t taps_v, const void* d_lut,
+                        int32_t patch, int32_t merge, int32_t temporal, void* d_patches, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!d_frames || !d_lut || !d_patches) return VQS_ERR_INVALID;
+    const MediaShape m = media_shape(n, T, H, W, rh, rw, patch, merge, temporal);
+    if (!m.ok) return VQS_ERR_INVALID;
+    const bool horiz = rw != W, vert = rh != H;
+    if (horiz && (!d_x0_h || !d_k_h || taps_h <= 0)) return VQS_ERR_INVALID;
+    if (vert && (!d_x0_v || !d_k_v || taps_v <= 0)) return VQS_ERR_INVALID;
+    if (horiz && (!d_ws || ws_bytes < m.h_bytes)) return VQS_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned char* src = (const unsigned char*)d_frames;
+    if (horiz) {
+        if (vqs::launch_qwen_resize_h(src, (unsigned char*)d_ws, d_x0_h, d_k_h, taps_h, (long long)n * T * H, W, rw, st) != hipSuccess) return VQS_ERR_HIP;
+        src = (const unsigned char*)d_ws;
+    }
+    vqs::QwenPatchRows p{src, vert ? d_x0_v : nullptr, vert ? d_k_v : nullptr, vert ? taps_v : 0, (const bf16_t*)d_lut, (bf16_t*)d_patches, m.rows,
+                         T, H, rw, patch, merge, temporal, m.t, m.gh, m.gw, 3 * temporal * patch * patch};
+    return vqs::launch_qwen_patch_rows(p, st) == hipSuccess ? VQS_OK : VQS_ERR_HIP;
+}
+
+}  // extern "C"

@@ -11,8 +11,10 @@ batch 1, :190), the prefill runs on libvqs_hip (include/vqs_qwen.h; no KV cache:
 prompt + k generated tokens), the softmax + gather run in the library's score head, frame resizing / patch flattening
 are restated here instead of going through ``qwen_vl_utils`` + the HF processor (neither is installable offline).
 
-Input support: ``.npy`` arrays ([H,W,3] image or [T,H,W,3] frames, as qwen2vl_model.py:145-155) and image files; video
-container files need decord/ffmpeg (absent) -> NotImplementedError.  Any frame size smart_resize produces is accepted
+Input support: ``.npy`` arrays ([H,W,3] image or [T,H,W,3] frames, as qwen2vl_model.py:145-155), the same arrays IN MEMORY (uint8
+``np.ndarray`` entries beside paths: a clip that was just generated needs no file) and image files; video container files need
+decord/ffmpeg (absent) -> NotImplementedError.  ``device_preprocess=True`` moves everything between the decoded uint8 frames and the
+tower to the GPU (QwenEngine.patches_from_frames, include/vqs_qwen.h vqs_qwen_patches_u8), bitwise the host path.  Any frame size smart_resize produces is accepted
 (partial attention windows at the frame edge are handled by the engine's padded windowed layout).
 """
 from __future__ import annotations
@@ -27,6 +29,7 @@ from PIL import Image
 
 from ...constants import HF_CACHE_DIR
 from ...qwen import Qwen25VLConfig, get_qwen_config
+from ...qwen.media import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD, normalize_frames  # noqa: F401  (the constants are part of this module's interface)
 from .vqa_model import VQAScoreModel
 
 QWEN25_VL_MODELS = {
@@ -34,8 +37,6 @@ QWEN25_VL_MODELS = {
 }
 default_question_template = 'Does this figure show "{}"? Please answer Yes or No.'     # qwen2vl_model.py:173
 default_answer_template = 'Yes'
-OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
-OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 VIDEO_FILE_MAX_PIXELS = 360 * 420      # qwen2vl_model.py:141-144: ONLY for video container paths (not supported here)
 # qwen_vl_utils (not installable here) resizes BEFORE the HF processor (the reference then passes do_resize=False,
 # qwen2vl_model.py:208-216): its defaults are IMAGE_FACTOR = 28, MIN_PIXELS = 4*28*28, MAX_PIXELS = 16384*28*28
@@ -126,13 +127,16 @@ class Qwen25VLModel(VQAScoreModel):
 
     def __init__(self, model_name='qwen2.5-vl-7b', device='cuda', cache_dir=HF_CACHE_DIR, checkpoint: Optional[str] = None,
                  weights=None, tokenizer=None, config: Optional[Qwen25VLConfig] = None, engine=None, max_batch: int = 32,
-                 seed: int = 0, num_workers: Optional[int] = None, share_prefix: bool = True):
+                 seed: int = 0, num_workers: Optional[int] = None, share_prefix: bool = True, *, device_preprocess: bool = False):
         """weights: None -> ``checkpoint`` (local HF directory of safetensors); 'seeded' -> seeded random weights at the
         architecture; or a dict.  tokenizer: object with ``encode(text, add_special_tokens=False) -> List[int]`` that maps
         the chat-template special tokens (HF protocol); None -> the checkpoint's tokenizer.  share_prefix: a batch in which a
         medium has several questions runs its prompt prefix (chat header + vision run + <|vision_end|>) through the language
-        model once (QwenEngine.score_shared; bitwise the same scores); False = every pair runs its whole prompt."""
+        model once (QwenEngine.score_shared; bitwise the same scores); False = every pair runs its whole prompt.  device_preprocess: resize,
+        normalise and flatten the uint8 frames on the GPU (QwenEngine.patches_from_frames: bitwise the host path `preprocess`, which engines
+        without that method keep)."""
         self.share_prefix = bool(share_prefix)
+        self.device_preprocess = bool(device_preprocess)
         assert config is not None or model_name in QWEN25_VL_MODELS, f"Model {model_name} not found in QWEN25_VL_MODELS"
         self._cfg = config if config is not None else get_qwen_config(QWEN25_VL_MODELS[model_name]['config'])
         self._weights_arg, self._tokenizer_arg, self._checkpoint, self._engine_arg = weights, tokenizer, checkpoint, engine
@@ -180,10 +184,16 @@ class Qwen25VLModel(VQAScoreModel):
         self.engine = QwenEngine(self.cfg, weights, device=dev)
 
     # ------------------------------------------------------------------ host-side preparation
-    def load_images(self, paths: List[str], fps: float = None) -> List[Dict]:
-        """-> [{'type': 'image'|'video', 'frames': uint8 [T,H,W,3]}] (qwen2vl_model.py:135-158)."""
+    def load_images(self, paths: List, fps: float = None) -> List[Dict]:
+        """-> [{'type': 'image'|'video', 'frames': uint8 [T,H,W,3]}] (qwen2vl_model.py:135-158).  An entry is a path or a uint8 np.ndarray
+        ([H,W,3] image or [T,H,W,3] frames: the rules of a .npy file of that shape, without the file)."""
         out = []
         for path in paths:
+            if isinstance(path, np.ndarray):
+                if path.dtype != np.uint8 or path.ndim not in (3, 4) or path.shape[-1] != 3:
+                    raise ValueError(f"an in-memory medium must be a uint8 [H,W,3] image or [T,H,W,3] frame array, got {path.dtype} {path.shape}")
+                out.append({'type': 'image', 'frames': path[None]} if path.ndim == 3 else {'type': 'video', 'frames': path})
+                continue
             low = str(path).lower()
             if low.endswith(('.mp4', '.avi', '.mov', '.mkv')):
                 raise NotImplementedError("video container files need decord/ffmpeg, which this environment does not have; "
@@ -200,6 +210,10 @@ class Qwen25VLModel(VQAScoreModel):
                 out.append({'type': 'image', 'frames': np.asarray(Image.open(path).convert('RGB'))[None]})
         return out
 
+    def _resized_hw(self, H: int, W: int) -> Tuple[int, int]:
+        v = self.cfg.vision
+        return smart_resize(H, W, factor=v.patch * v.spatial_merge, min_pixels=QVU_MIN_PIXELS, max_pixels=QVU_MAX_PIXELS)
+
     def preprocess(self, item: Dict) -> Tuple[torch.Tensor, Tuple[int, int, int]]:
         """Resize (smart_resize to multiples of 28), rescale, CLIP-normalise, flatten -> (patches fp32 [N, 1176], (t, h, w)).
         Frame lists from a 4-D .npy carry NO max_pixels in the reference's message (qwen2vl_model.py:151-153; the
@@ -208,23 +222,28 @@ class Qwen25VLModel(VQAScoreModel):
         v = self.cfg.vision
         frames = item['frames']
         H, W = frames.shape[1:3]
-        factor = v.patch * v.spatial_merge
-        rh, rw = smart_resize(H, W, factor=factor, min_pixels=QVU_MIN_PIXELS, max_pixels=QVU_MAX_PIXELS)
+        rh, rw = self._resized_hw(H, W)
         if (rh, rw) != (H, W):
             frames = np.stack([np.asarray(Image.fromarray(f).resize((rw, rh), Image.BICUBIC)) for f in frames])
-        x = torch.from_numpy(np.ascontiguousarray(frames)).permute(0, 3, 1, 2).to(torch.float32) * (1.0 / 255.0)
-        mean = torch.tensor(OPENAI_CLIP_MEAN).view(1, 3, 1, 1)
-        std = torch.tensor(OPENAI_CLIP_STD).view(1, 3, 1, 1)
-        return patchify((x - mean) / std, v.patch, v.spatial_merge, v.temporal_patch)
+        return patchify(normalize_frames(frames), v.patch, v.spatial_merge, v.temporal_patch)
+
+    def _deferred(self, item: Dict):
+        """device_preprocess: what `preprocess` returns with the uint8 frames in the place of the patch rows -- _media_windows turns them
+        into patch rows on the device, a group of equal shapes at a time."""
+        v = self.cfg.vision
+        T, H, W = item['frames'].shape[:3]
+        rh, rw = self._resized_hw(H, W)
+        return item['frames'], (-(-T // v.temporal_patch), rh // v.patch, rw // v.patch)
 
     def _prepare_media(self, images, fps=None):
-        """Load and preprocess every DISTINCT medium once (same path string = same medium; the reference re-reads and re-encodes
-        the file for every prompt, score.py:104-106 + qwen2vl_model.py:190).  -> (prepared [(patches, grid)] per distinct medium,
-        kinds ['image'|'video'] per distinct medium, media_of [index into those] per sample)."""
-        first: Dict[str, int] = {}
+        """Load and preprocess every DISTINCT medium once (same path string, or the same in-memory array object = same medium; the reference
+        re-reads and re-encodes the file for every prompt, score.py:104-106 + qwen2vl_model.py:190).  -> (prepared [(patches, grid)] per
+        distinct medium, kinds ['image'|'video'] per distinct medium, media_of [index into those] per sample).  With device_preprocess (and
+        an engine that has the device front end) `patches` are the medium's uint8 frames: see _media_windows."""
+        first: Dict = {}
         media_of, uniq = [], []
         for p in images:
-            key = p if isinstance(p, str) else None
+            key = p if isinstance(p, str) else ('array', id(p)) if isinstance(p, np.ndarray) else None
             if key is not None and key in first:
                 media_of.append(first[key])
                 continue
@@ -233,14 +252,37 @@ class Qwen25VLModel(VQAScoreModel):
             media_of.append(len(uniq))
             uniq.append(p)
         items = self.load_images(uniq, fps)
+        if getattr(self, "device_preprocess", False) and hasattr(self.engine, "patches_from_frames"):
+            prepared = [self._deferred(it) for it in items]
         # decode/resize/patch-flatten on a thread pool (PIL and torch release the GIL in their inner loops)
-        if len(items) > 1 and self.num_workers > 1:
+        elif len(items) > 1 and self.num_workers > 1:
             from concurrent.futures import ThreadPoolExecutor
             with ThreadPoolExecutor(max_workers=min(self.num_workers, len(items))) as pool:
                 prepared = list(pool.map(self.preprocess, items))
         else:
             prepared = [self.preprocess(it) for it in items]
         return prepared, [it['type'] for it in items], media_of
+
+    def _window_patches(self, prepared, chunk):
+        """Patch rows of the media `chunk` (one grid), in that order.  Host path: the prepared fp32 rows.  device_preprocess: the media's uint8
+        frames, grouped by (frame count, source size) -- with the shared grid that fixes the target size -- one
+        QwenEngine.patches_from_frames call per group."""
+        if not isinstance(prepared[chunk[0]][0], np.ndarray):
+            return torch.cat([prepared[u][0] for u in chunk])
+        v = self.cfg.vision
+        g = prepared[chunk[0]][1]
+        groups: Dict[Tuple[int, ...], List[int]] = {}
+        for u in chunk:
+            groups.setdefault(tuple(prepared[u][0].shape[:3]), []).append(u)
+        rows_of = {}
+        for us in groups.values():
+            rows = self.engine.patches_from_frames([prepared[u][0] for u in us], (g[1] * v.patch, g[2] * v.patch))
+            if len(groups) == 1:
+                return rows
+            n_rows = rows.shape[0] // len(us)
+            for k, u in enumerate(us):
+                rows_of[u] = rows[k * n_rows: (k + 1) * n_rows]
+        return torch.cat([rows_of[u] for u in chunk])
 
     def _media_windows(self, prepared, media_of):
         """Walk the samples grid by grid, medium by medium: yields (grid, sample indices, {medium: merged vision tokens
@@ -255,7 +297,7 @@ class Qwen25VLModel(VQAScoreModel):
             us = list(by_medium)
             for s in range(0, len(us), self.max_batch):
                 chunk = us[s: s + self.max_batch]
-                merged = self.engine.encode_vision(torch.cat([prepared[u][0] for u in chunk]), [g] * len(chunk))
+                merged = self.engine.encode_vision(self._window_patches(prepared, chunk), [g] * len(chunk))
                 yield g, [i for u in chunk for i in by_medium[u]], {u: merged[k * n_tok: (k + 1) * n_tok] for k, u in enumerate(chunk)}
 
     def build_ids(self, question: str, kind: str, n_tokens: int) -> List[int]:

@@ -28,6 +28,8 @@ _SIGS = {
     "vqs_qwen_bind_weights": (_i32, [_vp, ctypes.POINTER(VqsWeightDesc), _i32, _vp, _sz, _vp]),
     "vqs_qwen_vision_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "vqs_qwen_encode_vision": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "vqs_qwen_media_workspace_bytes": (_sz, [_i32] * 6),
+    "vqs_qwen_patches_u8": (_i32, [_vp] + [_i32] * 6 + [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "vqs_qwen_score_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "vqs_qwen_profile_enable": (_i32, [_vp, _i32]),
     "vqs_qwen_profile_read": (_i32, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _i32]),
@@ -84,6 +86,8 @@ class QwenEngine:
                                                        self._packed.numel(), _stream_ptr()), "vqs_qwen_bind_weights")
             torch.cuda.synchronize()
         self._ws = None
+        self._stage = self._stage_free = self._lut = None      # patches_from_frames: pinned staging, its copy-done event, the bf16 table
+        self._media_tables = {}
 
     def set_option(self, name: str, value: int):
         """Execution-form switches of include/vqs_qwen.h (vqs_qwen_debug_option): "tail_precise" 1 (default) = the logits come from the
@@ -153,6 +157,79 @@ class QwenEngine:
                                                         d["sin_w"].data_ptr(), d["cos_f"].data_ptr(), d["sin_f"].data_ptr(), Np,
                                                         lay["win_len"], lay["frame_len"], out.data_ptr(), ws.data_ptr(), ws.numel(),
                                                         _stream_ptr()), "vqs_qwen_encode_vision")
+            return out
+
+    def _axis_tables(self, n_in: int, n_out: int):
+        """-> (device first taps, device weights, taps) of one resize axis, uploaded once per (n_in, n_out); (None, None, 0): the axis keeps its size."""
+        if n_in == n_out:
+            return None, None, 0
+        if (n_in, n_out) not in self._media_tables:
+            from .media import pillow_bicubic_tables
+            first, weights = pillow_bicubic_tables(n_in, n_out)
+            self._media_tables[(n_in, n_out)] = (torch.from_numpy(first.copy()).to(self.device), torch.from_numpy(weights.copy()).to(self.device),
+                                                 int(weights.shape[1]))
+        return self._media_tables[(n_in, n_out)]
+
+    def patches_from_frames(self, frames_u8, resized_hw: Tuple[int, int]) -> torch.Tensor:
+        """The media front end on the device (vqs_qwen_patches_u8): frames_u8 uint8 [n, T, H, W, 3] -- one array, or a sequence of n
+        [T, H, W, 3] arrays of one shape -- resized to resized_hw (smart_resize's result), normalised and flattened -> bf16
+        [n * t * h * w, patch_dim] on the device, bitwise Qwen25VLModel.preprocess + the bf16 cast of encode_vision.  The frames go up as
+        uint8 through a pinned staging buffer with a non-blocking copy."""
+        import numpy as np
+        clips = [frames_u8] if isinstance(frames_u8, np.ndarray) and frames_u8.ndim == 5 else list(frames_u8)
+        clips = [np.asarray(c) for c in clips]
+        first = clips[0][0] if clips[0].ndim == 5 else clips[0]
+        T, H, W, C = first.shape
+        n = sum(c.shape[0] if c.ndim == 5 else 1 for c in clips)
+        if C != 3 or any(c.dtype != np.uint8 or tuple(c.shape[-4:]) != (T, H, W, 3) for c in clips):
+            raise VqsError("patches_from_frames expects uint8 [n, T, H, W, 3] frames of one shape")
+        v = self.cfg.vision
+        rh, rw = int(resized_hw[0]), int(resized_hw[1])
+        if rh % v.patch or rw % v.patch:
+            raise VqsError(f"resized size {rh} x {rw} is not a multiple of the patch size")
+        nbytes = n * T * H * W * 3
+        with torch.cuda.device(self.device):
+            dev = self.device
+            if self._stage is None or self._stage.numel() < nbytes:
+                if self._stage_free is not None:
+                    self._stage_free.synchronize()
+                self._stage = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+                self._stage_free = torch.cuda.Event()
+            else:
+                self._stage_free.synchronize()          # the previous call's copy has left the staging buffer
+            host = self._stage.numpy()
+            jobs, off = [], 0
+            for c in clips:
+                jobs.append((off, c))
+                off += c.size
+
+            def put(job):
+                host[job[0]: job[0] + job[1].size] = job[1].reshape(-1)
+
+            if nbytes >= (32 << 20) and len(jobs) > 1:          # numpy's copy releases the GIL
+                from concurrent.futures import ThreadPoolExecutor
+                with ThreadPoolExecutor(max_workers=min(8, len(jobs))) as pool:
+                    list(pool.map(put, jobs))
+            else:
+                for job in jobs:
+                    put(job)
+            d_frames = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            d_frames.copy_(self._stage[:nbytes], non_blocking=True)
+            self._stage_free.record()
+            if self._lut is None:
+                from .media import normalize_lut
+                self._lut = normalize_lut().to(dev)
+            x0h, kh, th = self._axis_tables(W, rw)
+            x0v, kv, tv = self._axis_tables(H, rh)
+            t = -(-T // v.temporal_patch)
+            out = torch.empty(n * t * (rh // v.patch) * (rw // v.patch), v.patch_dim, dtype=torch.bfloat16, device=dev)
+            ws = self._workspace(self.lib.vqs_qwen_media_workspace_bytes(n, T, H, W, rh, rw))
+            ptr = lambda x: None if x is None else x.data_ptr()      # noqa: E731
+            rc = self.lib.vqs_qwen_patches_u8(d_frames.data_ptr(), n, T, H, W, rh, rw, ptr(x0h), ptr(kh), th, ptr(x0v), ptr(kv), tv,
+                                              self._lut.data_ptr(), v.patch, v.spatial_merge, v.temporal_patch, out.data_ptr(), ws.data_ptr(),
+                                              ws.numel(), _stream_ptr())
+            if rc != 0:
+                raise VqsError(f"vqs_qwen_patches_u8 failed ({rc})")
             return out
 
     def _upload(self, lay, keys=("vis_slot", "seq_len", "last_row", "cos", "sin")):
