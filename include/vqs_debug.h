@@ -62,11 +62,17 @@ int vqs_debug_norm16(int32_t kind, float* d_x, const void* d_delta, const void* 
  *   vqs_debug_qwen_attention_suffix: attn_suffix_hd_kernel, query rows [q0, S) only: q [B, H, Sq, 128] (row r = position q0 + r, Sq >= S - q0),
  *     k / v [B, Hkv, S, 128], out [B*Sq, H*128]; q0 a multiple of 32
  *   vqs_debug_qwen_kv_assemble: qwen_kv_assemble_kernel: dk / dv [B, Hkv, Lp + Ls, 128] from pk / pv [U, Hkv, Lp, 128] (medium media_idx[b];
- *     outside [0, U): zero rows) and sk / sv [B, Hkv, Ls, 128] */
+ *     outside [0, U): zero rows) and sk / sv [B, Hkv, Ls, 128]
+ *   vqs_debug_attention_hd: every form of attn_fwd_hd_kernel<128, CAUSAL, F16>: fills the launch's parameter block (head width 128) and calls
+ *     launch_attention, nothing else.  causal = 0: the vision tower's form; out_hd (0 = 128, else a multiple of 4 up to 128): the lanes of a head
+ *     that leave, out is then [B*S, H*out_hd] (the tower's 80-lane compact output); d_key_len may be NULL (every sample has S keys); Hkv = 0
+ *     means H.  A shape the launcher refuses comes back as VQS_ERR_INVALID and nothing is launched. */
 int vqs_debug_qwen_attention(const void* d_q, const void* d_k, const void* d_v, void* d_out, const int32_t* d_key_len, int32_t B, int32_t H, int32_t Hkv,
                              int32_t S, float scale, int32_t f16, void* stream);
 int vqs_debug_qwen_attention_suffix(const void* d_q, const void* d_k, const void* d_v, void* d_out, const int32_t* d_key_len, int32_t B, int32_t H,
                                     int32_t Hkv, int32_t S, int32_t Sq, int32_t q0, float scale, int32_t f16, void* stream);
+int vqs_debug_attention_hd(const void* d_q, const void* d_k, const void* d_v, void* d_out, const int32_t* d_key_len, int32_t B, int32_t H, int32_t Hkv,
+                           int32_t S, float scale, int32_t causal, int32_t f16, int32_t out_hd, void* stream);
 int vqs_debug_qwen_kv_assemble(const void* d_pk, const void* d_pv, const void* d_sk, const void* d_sv, const int32_t* d_media_idx, void* d_dk, void* d_dv,
                                int32_t B, int32_t U, int32_t Hkv, int32_t Lp, int32_t Ls, void* stream);
 /* Single-launch test hooks of the Qwen2.5-VL decode-step kernels (csrc/qwen_decode.hip), on caller tensors; head width 128.

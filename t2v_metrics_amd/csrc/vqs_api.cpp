@@ -1310,6 +1310,14 @@ int vqs_debug_qwen_attention(const void* q, const void* k, const void* v, void* 
     return vqs::abi_code(vqs::launch_attention(a, (hipStream_t)stream));
 }
 
+int vqs_debug_attention_hd(const void* q, const void* k, const void* v, void* out, const int32_t* key_len, int32_t B, int32_t H, int32_t Hkv,
+                           int32_t S, float scale, int32_t causal, int32_t f16, int32_t out_hd, void* stream) {
+    if (!q || !k || !v || !out) return VQS_ERR_INVALID;
+    vqs::AttnParams a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, nullptr, key_len, B, H, S, scale};
+    a.hd = 128; a.Hkv = Hkv; a.causal = causal ? 1 : 0; a.out_hd = out_hd; a.f16 = f16 ? 1 : 0;
+    return vqs::abi_code(vqs::launch_attention(a, (hipStream_t)stream));
+}
+
 int vqs_debug_qwen_attention_suffix(const void* q, const void* k, const void* v, void* out, const int32_t* key_len, int32_t B, int32_t H,
                                     int32_t Hkv, int32_t S, int32_t Sq, int32_t q0, float scale, int32_t f16, void* stream) {
     if (!q || !k || !v || !out || !key_len) return VQS_ERR_INVALID;

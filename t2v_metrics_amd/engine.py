@@ -76,6 +76,7 @@ _SIGNATURES = {
     "vqs_debug_attention_f16": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i32, _c_i32, _c_i32, ctypes.c_float, _c_vp]),
     "vqs_debug_qwen_attention": (_c_i32, [_c_vp] * 5 + [_c_i32] * 4 + [ctypes.c_float, _c_i32, _c_vp]),
     "vqs_debug_qwen_attention_suffix": (_c_i32, [_c_vp] * 5 + [_c_i32] * 6 + [ctypes.c_float, _c_i32, _c_vp]),
+    "vqs_debug_attention_hd": (_c_i32, [_c_vp] * 5 + [_c_i32] * 4 + [ctypes.c_float] + [_c_i32] * 3 + [_c_vp]),
     "vqs_debug_qwen_kv_assemble": (_c_i32, [_c_vp] * 7 + [_c_i32] * 5 + [_c_vp]),
     "vqs_debug_qwen_decode_attention": (_c_i32, [_c_vp] * 5 + [_c_i64] + [_c_i32] * 4 + [ctypes.c_float, ctypes.c_float, _c_i32, _c_vp]),
     "vqs_debug_qwen_decode_rope_append": (_c_i32, [_c_vp] * 7 + [_c_i32] * 6 + [_c_vp]),
@@ -614,12 +615,15 @@ def gemm_rowscaled(A, W, epilogue: int, rowss, d_norm: int, eps: float, S: int =
     return out
 
 
-def attention(q, k, v, scale: float, bias_table=None, key_len=None):
-    """q, k, v [B,H,S,64] bf16 -> bf16 [B*S, H*64]; fp16 tensors run the fp16 instantiation (test hook vqs_debug_attention_f16)."""
+def attention(q, k, v, scale: float, bias_table=None, key_len=None, out=None):
+    """q, k, v [B,H,S,64] bf16 -> bf16 [B*S, H*64]; fp16 tensors run the fp16 instantiation (test hook vqs_debug_attention_f16).
+    out: a caller-owned contiguous tensor of at least B*S rows of H*64 (the tests' guard rows lie behind them)."""
     lib = load_library()
     B, H, S, d = q.shape
     assert d == 64 and k.dtype == q.dtype and v.dtype == q.dtype
-    out = torch.empty(B * S, H * 64, dtype=q.dtype, device=q.device)
+    if out is None:
+        out = torch.empty(B * S, H * 64, dtype=q.dtype, device=q.device)
+    assert out.dtype == q.dtype and out.is_contiguous() and out.numel() >= B * S * H * 64
     fn = lib.vqs_debug_attention_f16 if q.dtype == torch.float16 else lib.vqs_attention
     rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(bias_table), _ptr(key_len), B, H, S, scale, _stream_ptr())
     if rc != 0:
@@ -676,6 +680,23 @@ def attention_hd(q, k, v, scale: float, causal: bool = False, key_len=None):
                               1 if causal else 0, _stream_ptr())
     if rc != 0:
         raise VqsError(f"vqs_attention_hd failed ({rc})")
+    return out
+
+
+def debug_attention_hd(q, k, v, scale: float, causal: bool = False, key_len=None, out_hd: int = 0, out=None):
+    """Test hook (vqs_debug_attention_hd): q [B,H,S,128], k/v [B,Hkv,S,128] in bf16 or fp16 -> out of that type [B*S, H*(out_hd or 128)];
+    every form of attn_fwd_hd_kernel in one launch.  out: a caller-owned contiguous tensor of at least that size."""
+    lib = load_library()
+    B, H, S, d = q.shape
+    assert d == 128 and k.dtype == q.dtype and v.dtype == q.dtype and q.dtype in (torch.bfloat16, torch.float16)
+    width = H * (out_hd if 0 < out_hd <= d else d)      # an out_hd outside that is refused before anything is written
+    if out is None:
+        out = torch.empty(B * S, width, dtype=q.dtype, device=q.device)
+    assert out.dtype == q.dtype and out.is_contiguous() and out.numel() >= B * S * width
+    rc = lib.vqs_debug_attention_hd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(key_len), B, H, k.shape[1], S, scale,
+                                    1 if causal else 0, 1 if q.dtype == torch.float16 else 0, out_hd, _stream_ptr())
+    if rc != 0:
+        raise VqsError(f"vqs_debug_attention_hd failed ({rc})")
     return out
 
 
