@@ -164,6 +164,45 @@ int vqs_attention(const void* d_q, const void* d_k, const void* d_v, void* d_out
  * mean3 / std3 are HOST pointers to 3 floats. */
 int vqs_normalize_u8(const void* d_u8, void* d_out, int32_t N, int32_t H, int32_t W, const float* mean3, const float* std3,
                      void* stream);
+/* Image front end on the device: n in-memory uint8 images of ONE size -> the CLIP-normalised bf16 [n,3,S,S] the towers read, bit for bit
+ * what the host path computes (expand2square, Pillow's 8-bit bicubic shortest-edge resize, centre crop, then vqs_normalize_u8).  Free
+ * functions: no handle, no allocation, no synchronisation.  ALL geometry is folded into the arguments by the caller; the device only
+ * multiplies, adds, shifts, clamps and looks up:
+ *   d_src    uint8 [n,H,W,3]
+ *   canvas   a VIRTUAL [Hc,Wc] image that holds the source at offset (oy,ox) and the colour (color_r,g,b) everywhere else; it is never
+ *            materialised.  expand2square: Hc = Wc = max(H,W), oy = (Hc-H)/2, ox = (Wc-W)/2; no padding: the canvas is the image.
+ *   per axis the canvas length is resampled to resized_h / resized_w and the S outputs [crop, crop+S) of that are kept.  Where the
+ *            resized length differs from the canvas length the axis needs tables for exactly those S outputs: d_first int32 [S] (first
+ *            tap, canvas coordinates) and d_weights int32 [S,taps] (22-bit fixed point, rows zero-padded to taps) -- rows [crop, crop+S) of
+ *            Pillow's precompute_coeffs / normalize_coeffs_8bpc for canvas length -> resized length.  Where it is equal, the axis is not
+ *            resampled (its tables are ignored) and the outputs are canvas rows / columns [crop, crop+S).
+ *   passes   horizontal to a uint8 intermediate [n,rows,S,3] in d_ws, for the canvas rows [row0, row0+rows) only -- the rows the vertical
+ *            taps reach (every row index is clamped to that window; the call cannot compare the window with the vertical table,
+ *            which is device memory it never reads back: a window that is too small is memory-safe but gives wrong pixels -- the
+ *            binding derives it from the table, imagefront.image_plan), or a window that covers the kept rows where the height is not
+ *            resampled; then
+ *            vertical, lookup in d_lut (bf16 [3,256], the normalised value of every uint8 per channel) and store.  Each pass computes
+ *            clip8(((1 << 21) + sum k * px) >> 22); every tap index is clamped to its canvas axis, so no table can steer a read outside
+ *            the source.
+ * vqs_images_workspace_bytes(n, rows, S): bytes of d_ws for a call with a horizontal pass (rows = 0: none, the minimum); 0 on bad arguments.
+ * vqs_images_u8 returns, BEFORE any launch, VQS_ERR_INVALID for: a null d_src / d_lut / d_out / geometry, a non-positive size, a colour
+ * outside [0,255], a source rectangle not inside the canvas, a crop window outside [0, resized length), a table missing where the length
+ * changes, a row window outside the canvas or not covering the kept rows, n > 65535 or a canvas wider than 16384 with a horizontal pass;
+ * VQS_ERR_WORKSPACE for a missing or short d_ws when there is a horizontal pass. */
+typedef struct vqs_image_geometry {
+    int32_t n, H, W;                       /* source images */
+    int32_t Hc, Wc, oy, ox;                /* virtual canvas and the source's offset in it */
+    int32_t color_r, color_g, color_b;     /* the canvas colour outside the source */
+    int32_t S;                             /* output size */
+    int32_t resized_h, resized_w;          /* canvas lengths after the resize */
+    int32_t crop_y, crop_x;                /* first kept output per axis */
+    int32_t taps_v, taps_h;                /* columns of the weight tables (ignored where the axis is not resampled) */
+    int32_t row0, rows;                    /* canvas rows the horizontal pass computes (ignored without a horizontal pass) */
+} vqs_image_geometry;
+size_t vqs_images_workspace_bytes(int32_t n, int32_t rows, int32_t S);
+int vqs_images_u8(const void* d_src, const vqs_image_geometry* geometry, const int32_t* d_first_h, const int32_t* d_weights_h,
+                  const int32_t* d_first_v, const int32_t* d_weights_v, const void* d_lut, void* d_out, void* d_ws, size_t ws_bytes,
+                  void* stream);
 
 /* Rotary position embedding (rotate-half), in place on d_x bf16 [B,H,S,hd]; d_cos / d_sin fp32 [B*S, half] hold the per-token
  * angles' cos / sin for dims i < half (dim i pairs with i + half) -- HF models/qwen2_5_vl/modeling_qwen2_5_vl.py:153-172

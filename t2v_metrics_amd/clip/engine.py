@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from ..engine import FP16_MAX_FINITE_ROUNDED, VqsError, _stream_ptr, load_library, normalize_u8
+from ..engine import FP16_MAX_FINITE_ROUNDED, VqsError, _stream_ptr, images_from_u8, load_library, normalize_u8
 from .config import ClipConfig
 
 _c_i32, _c_i64, _c_f32, _c_vp, _c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
@@ -178,6 +178,10 @@ class ClipEngine:
     def normalize_u8(self, x_u8: torch.Tensor, mean, std) -> torch.Tensor:
         with torch.cuda.device(self.device):
             return normalize_u8(x_u8.to(self.device), mean, std)
+
+    def images_from_u8(self, src_u8: torch.Tensor, size: int, pad: bool) -> torch.Tensor:
+        with torch.cuda.device(self.device):
+            return images_from_u8(src_u8.to(self.device), size, pad)
 
     def encode_images(self, pixels: torch.Tensor) -> torch.Tensor:
         """pixels [n, 3, S, S] (CLIP-normalised; cast to bf16) -> fp32 unit embeddings [n, embed_dim] on the device."""

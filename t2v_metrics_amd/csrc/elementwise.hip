@@ -1384,4 +1384,192 @@ hipError_t launch_qwen_patch_rows(const QwenPatchRows& p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Image front end of the CLIP-FlanT5 / CLIPScore rows (include/vqs.h vqs_images_u8): in-memory uint8 images of one size -> the bf16
+// [n, 3, S, S] pixels the towers read, bit for bit _imgprep.clip_preprocess_u8 + vqs_normalize_u8.  The host folds expand2square, the
+// shortest-edge resize and the centre crop into (a) a VIRTUAL canvas [Hc, Wc] that holds the source at (oy, ox) and one colour elsewhere --
+// never materialised -- and (b) per axis the rows [crop, crop + S) of Pillow's tables, i.e. only the S outputs the crop keeps, or no table
+// and a crop offset where the axis keeps its length.  Same integer passes as the Qwen front end above (clip8_q22), but sources here are
+// 1024 and more wide with 13 to 25 taps per output, so:
+//   horizontal  a workgroup stages its canvas rows in LDS -- 16-byte global loads, consecutive lanes on consecutive addresses, landing
+//               16-byte aligned in LDS through a per-row byte shift; the padding colour is filled in there -- and runs the tap loop out of
+//               LDS with no rectangle test.  Only the canvas rows the vertical taps reach ([row0, row0 + nrows)) are computed.
+//   vertical    a lane owns VEC consecutive x of one output row and ONE channel (channel fastest over lanes: adjacent lanes read adjacent
+//               bytes of the channel-interleaved intermediate), looks its VEC results up in the bf16 [3, 256] table and stores them as one
+//               16-byte word into the channel-first plane (VEC = 8); VEC = 1 for an S that 8 does not divide.
+// Every tap index is clamped to its canvas axis and then to the rows kept; the host pads the weight rows with zeros.
+// ------------------------------------------------------------------------------------------------
+constexpr int kImgRowsPerWg = 4;
+constexpr int kImgLdsMax = 64 * 1024;
+
+size_t images_u8_lds_bytes(int Wc, int* rows) {
+    const size_t row = ((size_t)Wc * 3 + 32 + 15) & ~(size_t)15;          // + 15 bytes of shift, + 15 of the last chunk's overhang
+    const int r = row * kImgRowsPerWg <= (size_t)kImgLdsMax ? kImgRowsPerWg : 1;
+    if (Wc <= 0 || row * r > (size_t)kImgLdsMax) return 0;
+    if (rows) *rows = r;
+    return row * r;
+}
+
+// canvas byte b of a staged row lives at row[shift + b]; the shift makes the 16-byte aligned global chunks land 16-byte aligned in LDS
+__device__ __forceinline__ int img_row_shift(const ImagesU8& p, int img, int cy, size_t* g0) {
+    const int sy = cy - p.oy;
+    if (sy < 0 || sy >= p.H) return -1;                                     // a row of padding only
+    *g0 = ((size_t)img * p.H + sy) * p.W * 3;
+    const int a = (int)(((uintptr_t)p.src + *g0) & 15);
+    return (a - p.ox * 3) & 15;
+}
+
+__global__ void __launch_bounds__(256) images_resize_h_kernel(ImagesU8 p, int rows_per_wg, int row_lds) {
+    extern __shared__ __align__(16) unsigned char img_lds[];
+    const int img = blockIdx.y;
+    const int r_first = blockIdx.x * rows_per_wg;                           // relative to row0
+    const int r_cnt = min(rows_per_wg, p.nrows - r_first);
+    const long long src_bytes = (long long)p.n * p.H * p.W * 3;
+    const int seg = p.W * 3, canvas = p.Wc * 3;
+    // 1. the source segments, 16 bytes per lane.  A chunk that is not wholly inside the source ARRAY (only the first of image 0 / the last
+    //    of image n - 1 can be) is read bytewise; a chunk that overhangs into a neighbouring row brings bytes the padding fill overwrites.
+    for (int r = 0; r < r_cnt; ++r) {
+        size_t g0 = 0;
+        const int shift = img_row_shift(p, img, p.row0 + r_first + r, &g0);
+        if (shift < 0) continue;
+        unsigned char* row = img_lds + (size_t)r * row_lds;
+        const int a = (int)(((uintptr_t)p.src + g0) & 15);
+        const int lds0 = shift + p.ox * 3 - a;                              // a multiple of 16, >= 0
+        const int chunks = (a + seg + 15) >> 4;
+        for (int j = threadIdx.x; j < chunks; j += 256) {
+            const long long gb = (long long)g0 - a + 16LL * j;
+            if (gb >= 0 && gb + 16 <= src_bytes) {
+                *reinterpret_cast<uint4*>(row + lds0 + 16 * j) = *reinterpret_cast<const uint4*>(p.src + gb);
+            } else {
+                for (int e = 0; e < 16; ++e)
+                    if (gb + e >= (long long)g0 && gb + e < (long long)g0 + seg) row[lds0 + 16 * j + e] = p.src[gb + e];
+            }
+        }
+    }
+    __syncthreads();
+    // 2. the padding colour around them (the whole row where the canvas row lies outside the source)
+    for (int r = 0; r < r_cnt; ++r) {
+        size_t g0 = 0;
+        const int shift = img_row_shift(p, img, p.row0 + r_first + r, &g0);
+        unsigned char* row = img_lds + (size_t)r * row_lds + max(shift, 0);
+        const int left = shift < 0 ? canvas : p.ox * 3;                     // bytes [0, left) and [right, canvas) are padding
+        const int right = shift < 0 ? canvas : (p.ox + p.W) * 3;
+        for (int b = threadIdx.x; b < left; b += 256) row[b] = (unsigned char)(p.color >> (8 * (b % 3)));
+        for (int b = right + threadIdx.x; b < canvas; b += 256) row[b] = (unsigned char)(p.color >> (8 * (b % 3)));
+    }
+    __syncthreads();
+    // 3. the taps, out of LDS: one (row, x) per lane and step, three channels each
+    for (int it = threadIdx.x; it < r_cnt * p.S; it += 256) {
+        const int r = it / p.S, x = it - r * p.S;
+        size_t g0 = 0;
+        const int shift = img_row_shift(p, img, p.row0 + r_first + r, &g0);
+        const unsigned char* row = img_lds + (size_t)r * row_lds + max(shift, 0);
+        const int* kk = p.kh + (size_t)x * p.taps_h;
+        const int first = min(max(p.x0h[x], 0), p.Wc - 1);
+        int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+        for (int i = 0; i < p.taps_h; ++i) {
+            const unsigned char* px = row + min(first + i, p.Wc - 1) * 3;
+            const int w = kk[i];
+            a0 += w * (int)px[0];
+            a1 += w * (int)px[1];
+            a2 += w * (int)px[2];
+        }
+        unsigned char* o = p.mid + (((size_t)img * p.nrows + r_first + r) * p.S + x) * 3;
+        o[0] = clip8_q22(a0);
+        o[1] = clip8_q22(a1);
+        o[2] = clip8_q22(a2);
+    }
+}
+
+// MID: read the horizontal pass's intermediate; else the virtual canvas itself (no horizontal pass), columns [crop_x, crop_x + S)
+template <bool VERT, bool MID, int VEC>
+__global__ void __launch_bounds__(256) images_resize_v_kernel(ImagesU8 p) {
+    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int groups = p.S / VEC;
+    if (id >= (long long)p.n * p.S * groups * 3) return;
+    const int c = (int)(id % 3);
+    long long t = id / 3;
+    const int g = (int)(t % groups);
+    t /= groups;
+    const int y = (int)(t % p.S);
+    const int img = (int)(t / p.S);
+    const int x = g * VEC;
+    const int pad = (p.color >> (8 * c)) & 255;
+    auto fetch = [&](int cy, int e) -> int {
+        if (MID) {
+            const int rr = min(max(cy - p.row0, 0), p.nrows - 1);
+            return p.mid[(((size_t)img * p.nrows + rr) * p.S + x + e) * 3 + c];
+        }
+        const int sy = cy - p.oy, sx = p.crop_x + x + e - p.ox;
+        if (sy < 0 || sy >= p.H || sx < 0 || sx >= p.W) return pad;
+        return p.src[(((size_t)img * p.H + sy) * p.W + sx) * 3 + c];
+    };
+    int val[VEC];
+    if (VERT) {
+        const int* kk = p.kv + (size_t)y * p.taps_v;
+        const int first = min(max(p.y0v[y], 0), p.Hc - 1);
+        int acc[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] = 1 << 21;
+        for (int i = 0; i < p.taps_v; ++i) {
+            const int cy = min(first + i, p.Hc - 1);
+            const int w = kk[i];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[e] += w * fetch(cy, e);
+        }
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) val[e] = clip8_q22(acc[e]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) val[e] = fetch(p.crop_y + y, e);
+    }
+    const bf16_t* lut = p.lut + c * 256;
+    bf16_t* o = p.out + (((size_t)img * 3 + c) * p.S + y) * p.S + x;
+    if (VEC == 8) {
+        uint4 w;
+        w.x = (uint32_t)lut[val[0]] | ((uint32_t)lut[val[1 % VEC]] << 16);
+        w.y = (uint32_t)lut[val[2 % VEC]] | ((uint32_t)lut[val[3 % VEC]] << 16);
+        w.z = (uint32_t)lut[val[4 % VEC]] | ((uint32_t)lut[val[5 % VEC]] << 16);
+        w.w = (uint32_t)lut[val[6 % VEC]] | ((uint32_t)lut[val[7 % VEC]] << 16);
+        *reinterpret_cast<uint4*>(o) = w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) o[e] = lut[val[e]];
+    }
+}
+
+template <bool VERT, bool MID>
+static void images_v_dispatch(const ImagesU8& p, int vec, dim3 grid, hipStream_t s) {
+    if (vec == 8) hipLaunchKernelGGL((images_resize_v_kernel<VERT, MID, 8>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((images_resize_v_kernel<VERT, MID, 1>), grid, dim3(256), 0, s, p);
+}
+
+hipError_t launch_images_u8(const ImagesU8& p, hipStream_t s) {
+    if (p.n <= 0 || p.S <= 0 || p.n > 65535 || !p.src || !p.lut || !p.out || (p.kh && (!p.mid || !p.x0h || p.taps_h <= 0 || p.nrows <= 0)) ||
+        (p.kv && (!p.y0v || p.taps_v <= 0)))
+        return hipErrorInvalidValue;
+    if (p.kh) {
+        int rows = 1;
+        const size_t lds = images_u8_lds_bytes(p.Wc, &rows);
+        if (!lds) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(images_resize_h_kernel, dim3((unsigned)((p.nrows + rows - 1) / rows), (unsigned)p.n), dim3(256), lds, s, p, rows,
+                           (int)(lds / rows));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    // 16-byte stores where S and the result's address allow them
+    const int vec = (p.S % 8 == 0 && ((uintptr_t)p.out & 15) == 0) ? 8 : 1;
+    const long long blocks = ((long long)p.n * p.S * (p.S / vec) * 3 + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks);
+    if (p.kv) {
+        if (p.kh) images_v_dispatch<true, true>(p, vec, grid, s);
+        else images_v_dispatch<true, false>(p, vec, grid, s);
+    } else {
+        if (p.kh) images_v_dispatch<false, true>(p, vec, grid, s);
+        else images_v_dispatch<false, false>(p, vec, grid, s);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace vqs

@@ -1436,6 +1436,49 @@ int vqs_normalize_u8(const void* d_u8, void* d_out, int32_t N, int32_t H, int32_
                ? VQS_OK : VQS_ERR_HIP;
 }
 
+size_t vqs_images_workspace_bytes(int32_t n, int32_t rows, int32_t S) {
+    if (n <= 0 || rows < 0 || S <= 0) return 0;
+    const size_t need = (size_t)n * (size_t)rows * (size_t)S * 3;
+    return std::max<size_t>((need + 255) & ~(size_t)255, 256);
+}
+
+int vqs_images_u8(const void* d_src, const vqs_image_geometry* g, const int32_t* d_first_h, const int32_t* d_weights_h, const int32_t* d_first_v,
+                  const int32_t* d_weights_v, const void* d_lut, void* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+    if (!d_src || !g || !d_lut || !d_out) return VQS_ERR_INVALID;
+    if (g->n <= 0 || g->n > 65535 || g->H <= 0 || g->W <= 0 || g->Hc <= 0 || g->Wc <= 0 || g->S <= 0 || g->resized_h <= 0 || g->resized_w <= 0)
+        return VQS_ERR_INVALID;
+    const int32_t rgb[3] = {g->color_r, g->color_g, g->color_b};
+    for (int32_t v : rgb)
+        if (v < 0 || v > 255) return VQS_ERR_INVALID;
+    // the source rectangle lies inside the canvas, the crop window inside the resized axis (sums in 64 bits: no wrap-around)
+    if (g->oy < 0 || g->ox < 0 || (long long)g->oy + g->H > g->Hc || (long long)g->ox + g->W > g->Wc) return VQS_ERR_INVALID;
+    if (g->crop_y < 0 || g->crop_x < 0 || (long long)g->crop_y + g->S > g->resized_h || (long long)g->crop_x + g->S > g->resized_w)
+        return VQS_ERR_INVALID;
+    const bool horiz = g->resized_w != g->Wc, vert = g->resized_h != g->Hc;
+    if (horiz && (!d_first_h || !d_weights_h || g->taps_h <= 0)) return VQS_ERR_INVALID;
+    if (vert && (!d_first_v || !d_weights_v || g->taps_v <= 0)) return VQS_ERR_INVALID;
+    if ((long long)g->n * g->H * g->W > (1LL << 40) / 3 || (long long)g->n * g->S * g->S > (1LL << 40) / 3) return VQS_ERR_INVALID;
+    if (horiz) {
+        if (g->Wc > 16384 || !vqs::images_u8_lds_bytes(g->Wc, nullptr)) return VQS_ERR_INVALID;
+        if (g->row0 < 0 || g->rows <= 0 || (long long)g->row0 + g->rows > g->Hc) return VQS_ERR_INVALID;
+        if (!vert && (g->row0 > g->crop_y || g->crop_y + g->S > g->row0 + g->rows)) return VQS_ERR_INVALID;
+        if (!d_ws || ws_bytes < (size_t)g->n * (size_t)g->rows * (size_t)g->S * 3) return VQS_ERR_WORKSPACE;
+    }
+    vqs::ImagesU8 p{};
+    p.src = (const unsigned char*)d_src;
+    p.n = g->n; p.H = g->H; p.W = g->W;
+    p.Hc = g->Hc; p.Wc = g->Wc; p.oy = g->oy; p.ox = g->ox;
+    p.color = rgb[0] | (rgb[1] << 8) | (rgb[2] << 16);
+    p.S = g->S;
+    p.x0h = horiz ? d_first_h : nullptr; p.kh = horiz ? d_weights_h : nullptr; p.taps_h = horiz ? g->taps_h : 0; p.crop_x = g->crop_x;
+    p.y0v = vert ? d_first_v : nullptr; p.kv = vert ? d_weights_v : nullptr; p.taps_v = vert ? g->taps_v : 0; p.crop_y = g->crop_y;
+    p.row0 = horiz ? g->row0 : 0; p.nrows = horiz ? g->rows : 0;
+    p.mid = horiz ? (unsigned char*)d_ws : nullptr;
+    p.lut = (const bf16_t*)d_lut;
+    p.out = (bf16_t*)d_out;
+    return vqs::launch_images_u8(p, (hipStream_t)stream) == hipSuccess ? VQS_OK : VQS_ERR_HIP;
+}
+
 int vqs_rope(void* x, const float* cos_t, const float* sin_t, int32_t B, int32_t H, int32_t S, int32_t hd, int32_t half,
              void* stream) {
     return vqs::launch_rope((bf16_t*)x, cos_t, sin_t, B, H, S, hd, half, (hipStream_t)stream) == hipSuccess ? VQS_OK : VQS_ERR_HIP;

@@ -353,6 +353,29 @@ struct QwenPatchRows {
     int T, Hs, rw, patch, merge, temporal, t, gh, gw, D;
 };
 hipError_t launch_qwen_patch_rows(const QwenPatchRows& p, hipStream_t s);
+// ---- image front end of the CLIP-FlanT5 / CLIPScore rows (elementwise.hip; include/vqs.h vqs_images_u8): uint8 sources of one size -> the
+// CLIP-normalised bf16 [n, 3, S, S] the towers read.  All geometry (expand2square, shortest-edge resize, centre crop) arrives folded into a
+// virtual canvas + per-axis tables for the S kept outputs; vqs_images_u8 has validated every field before this is launched.
+struct ImagesU8 {
+    const unsigned char* src;   // u8 [n, H, W, 3]
+    int n, H, W;
+    int Hc, Wc, oy, ox;         // canvas size; the source sits at (oy, ox), every other canvas pixel is `color`
+    int color;                  // r | g << 8 | b << 16
+    int S;
+    const int* x0h;             // horizontal tables [S], [S, taps_h] in canvas columns; kh == nullptr: no horizontal pass, output columns are
+    const int* kh;              //   canvas columns [crop_x, crop_x + S)
+    int taps_h, crop_x;
+    const int* y0v;             // vertical tables, canvas rows; kv == nullptr: output rows are canvas rows [crop_y, crop_y + S)
+    const int* kv;
+    int taps_v, crop_y;
+    int row0, nrows;            // canvas rows [row0, row0 + nrows) the horizontal pass keeps
+    unsigned char* mid;         // u8 [n, nrows, S, 3]: the horizontal pass's result (unused without one)
+    const bf16_t* lut;          // bf16 [3, 256]
+    bf16_t* out;                // bf16 [n, 3, S, S]
+};
+// dynamic LDS of the horizontal pass for a canvas row of Wc pixels staged `rows` at a time; 0: the row does not fit
+size_t images_u8_lds_bytes(int Wc, int* rows);
+hipError_t launch_images_u8(const ImagesU8& p, hipStream_t s);
 hipError_t launch_interleave_gate(const bf16_t* wi0, const bf16_t* wi1, bf16_t* dst, int F, int D, hipStream_t s);
 
 // ---- shared-prompt-prefix passes of the Qwen2.5-VL row (include/vqs_qwen.h vqs_qwen_prefix / vqs_qwen_score_suffix)

@@ -34,6 +34,12 @@ class VqsWeightDesc(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("d_data", _c_vp), ("numel", _c_i64)]
 
 
+class VqsImageGeometry(ctypes.Structure):
+    """include/vqs.h vqs_image_geometry"""
+    _fields_ = [(n, _c_i32) for n in ("n", "H", "W", "Hc", "Wc", "oy", "ox", "color_r", "color_g", "color_b", "S", "resized_h", "resized_w",
+                                      "crop_y", "crop_x", "taps_v", "taps_h", "row0", "rows")]
+
+
 class VqsError(RuntimeError):
     pass
 
@@ -58,6 +64,8 @@ _SIGNATURES = {
     "vqs_profile_report": (ctypes.c_char_p, [_c_vp]),
     "vqs_gemm": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp] + [_c_i32] * 10 + [_c_vp]),
     "vqs_normalize_u8": (_c_i32, [_c_vp, _c_vp, _c_i32, _c_i32, _c_i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _c_vp]),
+    "vqs_images_workspace_bytes": (_c_sz, [_c_i32, _c_i32, _c_i32]),
+    "vqs_images_u8": (_c_i32, [_c_vp, ctypes.POINTER(VqsImageGeometry), _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_sz, _c_vp]),
     "vqs_rope": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_vp]),
     "vqs_attention_hd": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_f32, _c_i32, _c_vp]),
     "vqs_gemm_rms": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i32, _c_f32, _c_f32, _c_i32, _c_i32, _c_i32,
@@ -403,6 +411,10 @@ class VqsEngine:
         with torch.cuda.device(self.device):
             return normalize_u8(x_u8.to(self.device), mean, std)
 
+    def images_from_u8(self, src_u8: torch.Tensor, size: int, pad: bool) -> torch.Tensor:
+        with torch.cuda.device(self.device):
+            return images_from_u8(src_u8.to(self.device), size, pad)
+
     def generate(self, feats: torch.Tensor, img_index: torch.Tensor, input_ids: torch.Tensor,
                  max_new_tokens: int = 16) -> torch.Tensor:
         """Greedy decoding -> int32 [B, max_new_tokens] on the device (every step executed; cut at the first EOS = 1 on
@@ -656,6 +668,61 @@ def normalize_u8(x_u8: torch.Tensor, mean, std) -> torch.Tensor:
     rc = lib.vqs_normalize_u8(x_u8.contiguous().data_ptr(), out.data_ptr(), N, H, W, m3, s3, _stream_ptr())
     if rc != 0:
         raise VqsError(f"vqs_normalize_u8 failed ({rc})")
+    return out
+
+
+def image_geometry(plan, n: int) -> VqsImageGeometry:
+    """imagefront.ImagePlan + the number of images -> the struct vqs_images_u8 reads"""
+    return VqsImageGeometry(n, plan.H, plan.W, plan.Hc, plan.Wc, plan.oy, plan.ox, plan.color[0], plan.color[1], plan.color[2], plan.S,
+                            plan.resized_h, plan.resized_w, plan.crop_y, plan.crop_x,
+                            0 if plan.weights_v is None else plan.weights_v.shape[1], 0 if plan.weights_h is None else plan.weights_h.shape[1],
+                            plan.row0, plan.rows)
+
+
+_IMAGE_TABLES: Dict[tuple, tuple] = {}          # (device, H, W, S, pad) -> (plan, device copies of its four tables); bounded
+_IMAGE_TABLES_MAX = 32
+_IMAGE_LUT: Dict[torch.device, torch.Tensor] = {}
+
+
+def _image_tables(device: torch.device, H: int, W: int, S: int, pad: bool):
+    key = (device, H, W, S, bool(pad))
+    hit = _IMAGE_TABLES.get(key)
+    if hit is None:
+        from .imagefront import image_plan
+        plan = image_plan(H, W, S, bool(pad))
+        up = lambda a: None if a is None else torch.from_numpy(a.copy()).to(device)      # noqa: E731
+        hit = (plan, up(plan.first_h), up(plan.weights_h), up(plan.first_v), up(plan.weights_v))
+        while len(_IMAGE_TABLES) >= _IMAGE_TABLES_MAX:
+            _IMAGE_TABLES.pop(next(iter(_IMAGE_TABLES)), None)       # the oldest entry
+        _IMAGE_TABLES[key] = hit
+    return hit
+
+
+def images_from_u8(src_u8: torch.Tensor, size: int, pad: bool) -> torch.Tensor:
+    """The image front end on the device (vqs_images_u8): uint8 [n, H, W, 3] RGB images of one size on the GPU -> bf16 [n, 3, size, size],
+    bitwise normalize_u8 of _imgprep.clip_preprocess_u8 (pad: expand2square with the CLIP mean colour first).  The tables of a
+    (H, W, size, pad) live on the device in a small bounded cache; the workspace comes from torch."""
+    lib = load_library()
+    if src_u8.dim() != 4 or src_u8.shape[3] != 3 or src_u8.dtype != torch.uint8 or not src_u8.is_cuda or src_u8.numel() == 0:
+        raise VqsError("images_from_u8 expects a non-empty uint8 [n, H, W, 3] tensor on the GPU")
+    n, H, W, _ = src_u8.shape
+    dev = src_u8.device
+    src = src_u8.contiguous()
+    plan, fh, kh, fv, kv = _image_tables(dev, H, W, int(size), pad)
+    if dev not in _IMAGE_LUT:
+        from .qwen.media import normalize_lut
+        _IMAGE_LUT[dev] = normalize_lut().to(dev)
+    lut = _IMAGE_LUT[dev]
+    geo = image_geometry(plan, n)
+    out = torch.empty(n, 3, plan.S, plan.S, dtype=torch.bfloat16, device=dev)
+    need = lib.vqs_images_workspace_bytes(n, plan.rows if kh is not None else 0, plan.S)
+    if need == 0:
+        raise VqsError(f"vqs_images_workspace_bytes refused n={n} rows={plan.rows} S={plan.S}")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    rc = lib.vqs_images_u8(src.data_ptr(), ctypes.byref(geo), _ptr(fh), _ptr(kh), _ptr(fv), _ptr(kv), lut.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                           ws.numel(), _stream_ptr())
+    if rc != 0:
+        raise VqsError(f"vqs_images_u8 failed ({rc}) for {n} images of {H} x {W} -> {plan.S}")
     return out
 
 

@@ -11,6 +11,8 @@ What runs where:
   device (engine)    uint8 -> CLIP-normalised bf16 pixels, both towers, projection heads, L2 norm, cosine -- hand-written gfx950
                      kernels behind the C ABI (include/vqs_clip.h).  No torch.nn forward, no HF forward, no CPU fallback.
 Each distinct image and each distinct text of a call is encoded once; the reference runs a full forward per pair.
+An entry of ``images`` may also be an in-memory image (``PIL.Image``, uint8 ``np.ndarray`` / ``torch.Tensor`` [H, W, 3] RGB; imagefront.py);
+with ``device_preprocess=True`` their resize + crop runs on the GPU (include/vqs.h vqs_images_u8), bitwise the host path.
 """
 from __future__ import annotations
 
@@ -22,6 +24,7 @@ import torch
 
 from ...clip.config import CLIPSCORE_MODELS, get_clip_config
 from ...constants import HF_CACHE_DIR
+from ...imagefront import SourceStaging, dedupe, entry_image, is_path, load_pixels
 from .clipscore_model import CLIPScoreModel
 
 CLIP_MODELS = {name: {'config': name, 'hf_repo': get_clip_config(name).hf_repo} for name in CLIPSCORE_MODELS}
@@ -34,7 +37,7 @@ class CLIPModel(CLIPScoreModel):
 
     def __init__(self, model_name='openai:ViT-L-14-336', device='cuda', cache_dir=HF_CACHE_DIR, *, weights=None, tokenizer=None,
                  checkpoint: Optional[str] = None, config=None, max_images: int = 256, max_texts: int = 1024, seed: int = 0, engine=None,
-                 num_workers: Optional[int] = None, engine_options: Optional[Dict[str, int]] = None):
+                 num_workers: Optional[int] = None, engine_options: Optional[Dict[str, int]] = None, device_preprocess: bool = False):
         """
         weights:    None -> load ``checkpoint`` (a local HF ``CLIPModel`` directory of safetensors); 'seeded' -> seeded random weights at the
                     exact architecture (benchmarks, tests); or a dict name -> tensor (HF CLIPModel state_dict names).
@@ -43,6 +46,8 @@ class CLIPModel(CLIPScoreModel):
         config:     a ClipConfig overriding the registry entry (tests use the tiny configurations).
         engine:     an already constructed engine-like object (tests inject a recording double).
         engine_options: options of include/vqs_clip.h, e.g. {'fp16': 0} for bf16 operands.
+        device_preprocess: True = the in-memory entries of a call are resized and cropped on the GPU (engine.images_from_u8), bitwise the
+                    host path; paths keep the host path.  Ignored by an engine without that method.
         """
         assert config is not None or model_name in CLIP_MODELS
         self._weights_arg, self._tokenizer_arg, self._checkpoint = weights, tokenizer, checkpoint
@@ -55,6 +60,8 @@ class CLIPModel(CLIPScoreModel):
             cores = os.cpu_count() or 1
         self.num_workers = min(32, cores) if num_workers is None else max(1, int(num_workers))
         self._pool = None
+        self.device_preprocess = bool(device_preprocess)
+        self._src_staging = SourceStaging()
         self.max_images, self.max_texts = int(max_images), int(max_texts)
         super().__init__(model_name=model_name, device=device, cache_dir=cache_dir)
 
@@ -93,7 +100,8 @@ class CLIPModel(CLIPScoreModel):
     # ------------------------------------------------------------------ host-side preparation
     def _preprocess_one_u8(self, path) -> np.ndarray:
         from ...preprocess import clip_preprocess_u8
-        return clip_preprocess_u8(self.image_loader(path), self.cfg.vision.image, False)
+        img = self.image_loader(path) if is_path(path) else entry_image(path)      # in-memory entries: the same pixels as a PIL image
+        return clip_preprocess_u8(img, self.cfg.vision.image, False)
 
     def _load_u8(self, image: Sequence[str]) -> torch.Tensor:
         S = self.cfg.vision.image
@@ -110,7 +118,15 @@ class CLIPModel(CLIPScoreModel):
     def load_images(self, image: List[str]) -> torch.Tensor:
         """Decode + shortest-edge bicubic resize + centre crop on the host; rescale + CLIP mean / std + bf16 on the GPU
         (vqs_normalize_u8, the fp32 arithmetic of HF CLIPImageProcessor) -> bf16 [N, 3, S, S] on the device."""
-        from ...preprocess import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD, clip_preprocess
+        on_gpu = str(self.device).startswith('cuda') and torch.cuda.is_available()
+        if self.device_preprocess and on_gpu and hasattr(self.engine, "images_from_u8"):
+            if not all(is_path(p) for p in image):      # the device front end, one call per source size; paths keep the host path
+                return load_pixels(self.engine, self.device, self._src_staging, image, self.cfg.vision.image, False, self._load_images_from_host,
+                                   self._pool)
+        return self._load_images_from_host(image)
+
+    def _load_images_from_host(self, image: List[str]) -> torch.Tensor:
+        from ...preprocess import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
         u8 = self._load_u8(image)
         if hasattr(self.engine, "normalize_u8") and str(self.device).startswith('cuda') and torch.cuda.is_available():
             return self.engine.normalize_u8(u8.to(self.device), OPENAI_CLIP_MEAN, OPENAI_CLIP_STD)
@@ -143,11 +159,10 @@ class CLIPModel(CLIPScoreModel):
     def encode(self, images: Sequence[str], texts: Sequence[str]):
         """Distinct images and texts, each encoded once -> (image embeddings [U, E], text embeddings [V, E], image index per input,
         text index per input)."""
-        ui: Dict[str, int] = {}
         ut: Dict[str, int] = {}
-        img_ix = [ui.setdefault(str(p), len(ui)) for p in images]
+        paths, img_ix = dedupe(images)                # paths by str(p), in-memory images by identity; every entry checked first
         txt_ix = [ut.setdefault(t, len(ut)) for t in texts]
-        paths, utexts = list(ui.keys()), list(ut.keys())
+        utexts = list(ut.keys())
         img = [self.engine.encode_images(self.load_images(paths[s: s + self.max_images])) for s in range(0, len(paths), self.max_images)]
         txt = []
         for s in range(0, len(utexts), self.max_texts):

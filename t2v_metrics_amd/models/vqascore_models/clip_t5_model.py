@@ -14,6 +14,9 @@ What runs where:
 Differences from the reference wrapper that do not change results:
   * identical image paths inside one call are decoded and encoded once (the reference re-encodes the same image
     for every text: score.py:105-106);
+  * an entry of ``images`` may also be an in-memory image -- a ``PIL.Image``, a uint8 ``np.ndarray`` [H, W, 3] RGB or a uint8
+    ``torch.Tensor`` [H, W, 3] (imagefront.py): same pixels, same score as the image read from a lossless file.  With
+    ``device_preprocess=True`` their pad / resize / crop runs on the GPU (include/vqs.h vqs_images_u8), bitwise the host path;
   * ``forward`` returns a CPU fp32 tensor like the reference; ``forward_grid`` scores an M x N grid in one pass.
 """
 from __future__ import annotations
@@ -26,6 +29,7 @@ import torch
 
 from ...config import get_config
 from ...constants import (CONTEXT_LEN, DEFAULT_IMAGE_TOKEN, HF_CACHE_DIR, IGNORE_INDEX, IMAGE_TOKEN_INDEX, SYSTEM_MSG)
+from ...imagefront import SourceStaging, check_entry, dedupe, entry_image, is_path, load_pixels
 from .mm_utils import t5_tokenizer_image_token
 from .vqa_model import VQAScoreModel
 
@@ -58,7 +62,8 @@ class CLIPT5Model(VQAScoreModel):
     def __init__(self, model_name='clip-flant5-xxl', device='cuda', cache_dir=HF_CACHE_DIR, *, weights=None,
                  tokenizer=None, checkpoint: Optional[str] = None, config=None, max_pairs: int = 256,
                  max_images: int = 256, seed: int = 0, engine=None, num_workers: Optional[int] = None,
-                 vision_tower: Optional[str] = None, image_workers: str = "process", engine_options: Optional[Dict[str, int]] = None):
+                 vision_tower: Optional[str] = None, image_workers: str = "process", engine_options: Optional[Dict[str, int]] = None,
+                 device_preprocess: bool = False):
         """
         engine_options: execution-form options of the HIP engine (include/vqs.h vqs_set_option), e.g. {'vit_fp16': 0, 'enc_fp16': 0} to run
                     the vision tower and the T5 encoder's attention side on bf16 operands (the reference's dtype) instead of IEEE fp16.
@@ -74,6 +79,9 @@ class CLIPT5Model(VQAScoreModel):
         image_workers: "process" (default) = worker processes (t2v_metrics_amd/imgpool.py: PIL decodes under the GIL, so
                     only processes scale the decode -- what a rank needs when it has 1/8 of the host's cores), "thread" = the
                     thread pool of rounds 1-3.  A custom ``self.image_loader`` always runs on threads (workers cannot see it).
+        device_preprocess: True = the in-memory entries of a call (PIL / ndarray / tensor) are padded, resized and cropped on the GPU
+                    (engine.images_from_u8: uint8 sources up through pinned staging, or straight from device tensors), bitwise the host
+                    path; paths keep the host path (decode dominates them).  Ignored by an engine without that method.
         """
         assert config is not None or model_name in CLIP_T5_MODELS
         self._weights_arg, self._tokenizer_arg, self._checkpoint = weights, tokenizer, checkpoint
@@ -89,6 +97,8 @@ class CLIPT5Model(VQAScoreModel):
         if image_workers not in ("process", "thread"):
             raise ValueError("image_workers must be 'process' or 'thread'")
         self.image_workers = image_workers
+        self.device_preprocess = bool(device_preprocess)
+        self._src_staging = SourceStaging()
         self._pool = None
         self._proc_pool = None
         self._staging = [None, None]              # two pinned uint8 staging buffers + the event of their last H2D copy
@@ -157,14 +167,17 @@ class CLIPT5Model(VQAScoreModel):
             self._pool = ThreadPoolExecutor(max_workers=self.num_workers, thread_name_prefix="vqs-img")
         return self._pool
 
+    def _open(self, entry):
+        """A path through the decode hook; an in-memory entry (imagefront.py) as the RGB PIL image of the same pixels."""
+        return self.image_loader(entry) if is_path(entry) else entry_image(entry)
+
     def _preprocess_one(self, path) -> torch.Tensor:
         from ...preprocess import clip_preprocess
-        img = self.image_loader(path)
-        return torch.from_numpy(clip_preprocess(img, self.cfg.vision.image, self.image_aspect_ratio == 'pad'))
+        return torch.from_numpy(clip_preprocess(self._open(path), self.cfg.vision.image, self.image_aspect_ratio == 'pad'))
 
     def _preprocess_one_u8(self, path) -> np.ndarray:
         from ...preprocess import clip_preprocess_u8
-        return clip_preprocess_u8(self.image_loader(path), self.cfg.vision.image, self.image_aspect_ratio == 'pad')
+        return clip_preprocess_u8(self._open(path), self.cfg.vision.image, self.image_aspect_ratio == 'pad')
 
     def _load_images_host(self, image: List[str]) -> torch.Tensor:
         """Decode + pad to square + CLIP-preprocess on the host (thread pool) -> fp32 [N,3,S,S]."""
@@ -207,28 +220,46 @@ class CLIPT5Model(VQAScoreModel):
             # waiting for its reply costs more than it saves (a 512 x 512 PNG: 7-11 ms through the pool, tools/bench_call_latency.py); same bytes either way
             arr[0] = self._preprocess_one_u8(image[0])
             return k, out
-        if self._use_process_pool():
+        # worker processes cannot see an in-memory object: those entries run on the thread pool (Pillow's resize releases the GIL) while
+        # the paths of the same call keep the process pool; every result lands in its own row, so a mixed list keeps its order
+        todo = list(enumerate(image))
+        on_disk = [i for i, p in todo if is_path(p)]
+        if len(on_disk) > 1 and self._use_process_pool():
             if self._proc_pool is None:
                 from ...imgpool import ImageProcessPool
                 self._proc_pool = ImageProcessPool(self.num_workers)
-            np.copyto(arr, self._proc_pool.load_u8(list(image), S, self.image_aspect_ratio == 'pad'))
-            return k, out
+            loaded = self._proc_pool.load_u8([image[i] for i in on_disk], S, self.image_aspect_ratio == 'pad')
+            if len(on_disk) == len(image):
+                np.copyto(arr, loaded)
+                return k, out
+            arr[on_disk] = loaded
+            todo = [(i, p) for i, p in todo if not is_path(p)]
         pool = self._executor()
 
         def work(i_path):
             arr[i_path[0]] = self._preprocess_one_u8(i_path[1])       # the copy into the staging buffer happens in the worker
 
-        if pool is not None:
-            list(pool.map(work, enumerate(image)))
+        if pool is not None and len(todo) > 1:
+            list(pool.map(work, todo))
         else:
-            for ip in enumerate(image):
+            for ip in todo:
                 work(ip)
         return k, out
 
     def load_images(self, image: List[str]) -> torch.Tensor:
         """Decode + pad to square + CLIP-preprocess; returns bf16 [N,3,S,S] on the device.  With the HIP engine the
         per-pixel float work (rescale, normalise, bf16) runs on the GPU from a uint8 staging buffer (1/4 of the H2D
-        bytes, no GIL-bound numpy arithmetic); test doubles without ``normalize_u8`` get the host float path."""
+        bytes, no GIL-bound numpy arithmetic); test doubles without ``normalize_u8`` get the host float path.  With device_preprocess
+        the in-memory entries take the device front end, one engine.images_from_u8 call per source size; paths keep the host path."""
+        on_gpu = str(self.device).startswith('cuda') and torch.cuda.is_available()
+        if self.device_preprocess and on_gpu and hasattr(self.engine, "images_from_u8"):
+            if not all(is_path(p) for p in image):
+                return load_pixels(self.engine, self.device, self._src_staging, image, self.cfg.vision.image, self.image_aspect_ratio == 'pad',
+                                   self._load_images_from_host, self._executor())
+        return self._load_images_from_host(image)
+
+    def _load_images_from_host(self, image: List[str]) -> torch.Tensor:
+        """The host front end (pad, PIL resize, crop on the CPU; the float tail on the GPU where the engine has it)."""
         if hasattr(self.engine, "normalize_u8") and str(self.device).startswith('cuda') and torch.cuda.is_available():
             from ...preprocess import OPENAI_CLIP_MEAN, OPENAI_CLIP_STD
             k, host = self._load_images_host_u8(image)
@@ -277,6 +308,8 @@ class CLIPT5Model(VQAScoreModel):
         operands after an fp16 execution option produced a non-finite score -- see the end of this method.)"""
         n = len(questions)
         assert len(answers) == n and len(pair_image) == n
+        for p in images:
+            check_entry(p)               # a float array, a wrong rank, ...: named before any decode or engine call
         if n == 0:           # empty M x N grids are legal in the reference (score.py:104 builds a [M, N] tensor of zeros)
             empty = torch.zeros(0, dtype=torch.float32)
             return (empty, torch.zeros(0, 0, dtype=torch.float32)) if return_logprobs else empty
@@ -353,9 +386,8 @@ class CLIPT5Model(VQAScoreModel):
         assert len(images) == len(texts), "Number of images and texts must match"
         questions = [question_template.format(t) for t in texts]
         answers = [answer_template.format(t) for t in texts]
-        uniq: Dict[str, int] = {}
-        pair_image = [uniq.setdefault(str(p), len(uniq)) for p in images]
-        return self.score_pairs(list(uniq.keys()), pair_image, questions, answers, return_logprobs)
+        entries, pair_image = dedupe(images)          # paths by str(p), in-memory images by identity
+        return self.score_pairs(entries, pair_image, questions, answers, return_logprobs)
 
     def forward_grid(self, images: List[str], texts: List[str], question_template: str = default_question_template,
                      answer_template: str = default_answer_template) -> torch.Tensor:
@@ -363,10 +395,9 @@ class CLIPT5Model(VQAScoreModel):
         M, N = len(images), len(texts)
         questions = [question_template.format(t) for t in texts] * M
         answers = [answer_template.format(t) for t in texts] * M
-        uniq: Dict[str, int] = {}
-        img_ids = [uniq.setdefault(str(p), len(uniq)) for p in images]
+        entries, img_ids = dedupe(images)
         pair_image = [img_ids[i] for i in range(M) for _ in range(N)]
-        return self.score_pairs(list(uniq.keys()), pair_image, questions, answers).reshape(M, N)
+        return self.score_pairs(entries, pair_image, questions, answers).reshape(M, N)
 
     @torch.no_grad()
     def generate_ids(self, images: List[str], texts: List[str], max_new_tokens: int = 16, _retry: bool = False) -> List[List[int]]:
@@ -375,9 +406,7 @@ class CLIPT5Model(VQAScoreModel):
         assert len(images) == len(texts), "Number of images and texts must match"
         if not 1 <= max_new_tokens <= 512:
             raise ValueError("max_new_tokens must be in [1, 512]")
-        uniq: Dict[str, int] = {}
-        pair_image = [uniq.setdefault(str(p), len(uniq)) for p in images]
-        paths = list(uniq.keys())
+        paths, pair_image = dedupe(images)
         feats = torch.cat([self.engine.encode_images(self.load_images(paths[s: s + self.max_images]))
                            for s in range(0, len(paths), self.max_images)], 0)
         ids, _ = self.tokenize(texts, [""] * len(texts))
