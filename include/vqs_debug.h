@@ -28,15 +28,26 @@ int vqs_debug_heads_rows(int32_t row0, int32_t S, int32_t hx, int32_t hdim, int3
  * illegal ns falls back to 1) or a negative error. */
 int vqs_debug_tile_order(int32_t M, int32_t N, int32_t K, int32_t batch, int32_t gm, int32_t ns, int32_t grid, int32_t* out);
 /* Host-side test hook, no device access: the kernel family a vqs_gemm launch of this shape resolves to, by the launcher's own
- * function (gemm.hip gemm_form): 10 = the quad form (four waves, 16x16x32 MFMAs; operand offsets relative to the output tile, no
+ * function (gemm.hip gemm_plan, read through vqs_debug_gemm_plan below; bias-free, ldc = N): 10 = the quad form (four waves, 16x16x32 MFMAs; operand offsets relative to the output tile, no
  * size limit), 3 = an 8-wave persistent kernel (32-bit byte offsets into a batch entry's operands), 12 = the stream form (<= 128 rows
  * per batch entry, W streamed from HBM; bitwise the results of 3: one family), 13 = a quad call site's few-row launch in the slim form
  * (gemm_slim.inc, round 6: 128 x 128 tiles for launches whose 256 x 256 tiles leave most CUs idle; bitwise the results of 10: one family),
- * 0 = one tile per workgroup (64-bit pointers), -1 = not launchable.  Two properties the tests pin: the form of a bf16-result launch is a function of the
+ * 0 = one tile per workgroup (64-bit pointers), -1 = not launchable (the launcher's argument checks included: a refused variant, K not a multiple of 64, ...).  Two properties the tests pin: the form of a bf16-result launch is a function of the
  * epilogue and the WEIGHT's shape only, never of M (a pair's bits must not depend on its batch), and an operand of 4 GiB or more
  * per batch entry never reaches a 32-bit kernel (it falls back to family 0 where that computes the same function, else -1). */
 int vqs_debug_gemm_form(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t epilogue, int32_t batch, int32_t variant,
                         int32_t S, int32_t inner, int32_t inner_kv);
+/* Host-side test hook, no device access: the whole plan of a GEMM launch, by the launcher's own function (gemm.hip gemm_plan, where the rule
+ * is stated).  launch[VQS_GEMM_PLAN_FIELDS] describes the launch by integers only (unused fields 0):
+ *   0 M, 1 N, 2 K, 3 lda, 4 ldw, 5 ldc, 6 epilogue, 7 batch, 8 variant (bits 0-7 as vqs_gemm), 9 S, 10 inner, 11 inner_kv, 12 hd, 13 hd_src, 14 Hkv, 15 operand type (GemmParams::f16, 0-4),
+ *   16 l2_touch override (0 by shape, 1 on, 2 off), 17 split_off (elements; 0 = no split result), 18 flags, 19 gate_act, 20 rowss_parts, 21 ldh;
+ *   flags: 1 bias present, 2 row scale (rowss_in) present, 4 no_stream, 8 rope cos table, 16 rope sin table, 32 the fused residual +
+ *   RMSNorm operands (hres, lnw, rowss_out) present, 64 a launch of an engine handle (its batched launches follow the library rule).
+ * Returns 1 and plan[0..4] = kernel family (0 tile, 1 tile ping-pong, 2 persistent, 3 persistent ping-pong, 4 stream, 5 quad, 6 slim:
+ * vqs_kernels.h GemmKernel), the persistent kernel's L2 touch (0 / 2), the operand type the kernel is instantiated for, workgroups,
+ * threads per workgroup; 0 where the launcher refuses the launch (hipErrorInvalidValue); VQS_ERR_INVALID for a bad call of the hook. */
+#define VQS_GEMM_PLAN_FIELDS 22
+int vqs_debug_gemm_plan(const int32_t* launch, int32_t n, int32_t* plan);
 /* Device-side test hook: the batched form of vqs_gemm that the engine's decoder launches (entry z reads A + z*sA, W + z*sW and
  * writes C + z*sC, strides in elements; EPI_F32 or EPI_BF16 only), with the split-bf16 result store (split_off != 0: the lo plane
  * bf16(acc - hi) goes to C + split_off) and no_stream = 1 keeping the launch off the stream form (csrc/gemm_stream.inc).  The

@@ -22,9 +22,8 @@
 #include <cstdlib>
 #include <type_traits>
 
-// Kernels of this file: variant 0 one tile per workgroup, 2 / 5 the ping-pong schedule, 3 / 11 persistent with the schedule
-// chosen by shape (3 hands the big bf16-result launches to the quad form of gemm_quad.inc).  The A/B forms of rounds 1-3
-// (register-staged, wave-specialised, wide, ring) and the ablation builds are in the git history only.
+// Kernels of this file: one tile per workgroup, persistent lock-step and persistent ping-pong; the quad, slim and stream forms are in
+// gemm_quad.inc, gemm_slim.inc and gemm_stream.inc.  Which of them a launch takes is decided by gemm_plan, at the end of this file.
 
 namespace vqs {
 
@@ -1241,12 +1240,6 @@ __global__ void __launch_bounds__(512) gemm_bf16_pingpong(const GemmParams p) {
 #undef VQS_WAIT_NEXT
 #undef VQS_WAIT_NONE
 
-// VQS_L2_TOUCH: 4 (default) = A-panel touch for N <= 2048; 3 = A and W panels for N <= 2048; 1 = A and W for every
-// lock-step launch; 0 = off
-static int l2_touch_mode() {
-    return 4;
-}
-
 // Which launches the quad form carries: a function of the epilogue and the WEIGHT's shape only (never of M).
 static bool quad_eligible_rt(const GemmParams& p, int epi) {
     if (!(epi == EPI_BF16 || epi == EPI_BF16_QGELU || epi == EPI_BF16_GELU || epi == EPI_GATED || epi == EPI_HEADS)) return false;
@@ -1260,190 +1253,164 @@ static bool quad_eligible_rt(const GemmParams& p, int epi) {
     }
     return true;
 }
-template <int EPI>
-static bool quad_eligible(const GemmParams& p) { return quad_eligible_rt(p, EPI); }
-// Kernel family a launch resolves to (host arithmetic, shared with the test hook vqs_debug_gemm_form): 10 quad form, 0 one tile per
-// workgroup (64-bit pointers), 3 an 8-wave persistent / ping-pong kernel or a lab form (32-bit byte offsets into a batch entry's
-// operands), -1 not launchable.  The 32-bit forms refuse operands of 4 GiB or more per batch entry; a plain single-entry launch
-// then falls back to the one-tile-per-workgroup kernel (same bits), anything else is an error -- never a wrapped offset.
-int gemm_form(const GemmParams& p, int epilogue, int variant) {
-    if (p.f16)      // fp16 operands: the quad form only (every 16-bit-result linear of the vision tower, the projector and -- option enc_fp16 --
-                    // the T5 encoder's attention side resolves to it); 1 = fp16 result (no gated epilogue), 2 = bf16 result (plain / gated only)
-    {
-        if ((variant == 3 || variant == 10) && quad_eligible_rt(p, epilogue))
-            return (p.f16 == 4 ? epilogue == EPI_BF16 : p.f16 == 3 ? epilogue != EPI_BF16_QGELU : p.f16 == 1 ? epilogue != EPI_GATED : (p.f16 == 2 && (epilogue == EPI_BF16 || epilogue == EPI_GATED))) ? 10 : -1;
-        if (p.f16 >= 3) return -1;      // the scaled families exist in the quad form only
-        // round 5: the batched / fp32-result launches of the decoder's cross-attention score path (option dec_fp16) -- plain epilogues of the
-        // stream form and of the persistent 8-wave kernel (bias-free, no row scale; fp32 result, fp16 result, bf16 / split-bf16 result)
-        if (variant != 3 || !(epilogue == EPI_BF16 || epilogue == EPI_F32) || p.bias != nullptr || p.rowss_in != nullptr) return -1;
-        if (p.f16 == 1 && p.split_off != 0) return -1;
-        if (stream_eligible(p, epilogue)) return 12;
-        const bool fit16 = (uint64_t)p.M * (uint64_t)p.lda * 2ull < (1ull << 32) && (uint64_t)p.N * (uint64_t)p.ldw * 2ull < (1ull << 32);
-        return fit16 ? 3 : -1;
-    }
-    if (epilogue == EPI_RESID_RMS) variant = variant == 5 ? 5 : 3;
-    const bool plain_v0 = !(p.hd > 64 || p.hd_src > 0 || p.inner_kv > 0 || p.Hkv > 0 || p.gate_act != 0 || (epilogue == EPI_GATED && p.bias != nullptr) || p.rowss_in != nullptr ||
-                            p.split_off != 0) &&
-                          p.batch <= 1 && epilogue != EPI_RESID_RMS;
-    if (variant == 0 || variant == 2 || variant == 1) return plain_v0 ? 0 : -1;
-    if (epilogue == EPI_HEADS && p.S < 8) return plain_v0 ? 0 : -1;
-    if ((variant == 3 || variant == 10) && quad_eligible_rt(p, epilogue)) return 10;       // first: a quad call site stays quad for every M
-    if ((variant == 3 || variant == 11) && stream_eligible(p, epilogue)) return 12;         // stream form: bitwise the 8-wave forms (gemm_stream.inc)
-    if (epilogue == EPI_HEADS && p.hd_src > 0 && p.hd_src != (p.hd > 0 ? p.hd : 64)) return -1;   // narrow heads in wide slots: quad form only
-    if (epilogue == EPI_F32_RESID) return p.batch <= 1 ? 0 : -1;
-    const bool fit = (uint64_t)p.M * (uint64_t)p.lda * 2ull < (1ull << 32) && (uint64_t)p.N * (uint64_t)p.ldw * 2ull < (1ull << 32);
-    if (fit) return 3;
-    return plain_v0 ? 0 : -1;
-}
 
-bool gemm_takes_slim(const GemmParams& p, int epilogue, int variant) {
-    return variant == 3 && !p.no_stream && gemm_form(p, epilogue, variant) == 10 && slim_eligible(p, epilogue);
-}
-
-template <int EPI>
-static hipError_t launch_epi(const GemmParams& p, int variant, hipStream_t stream) {   // NOLINT(variant is resolved below)
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
-    dim3 grid(tiles_m * tiles_n), block(512);
-    // variant 11 = the 8-wave forms by the round-1/2 shape rule for every launch (A/B against the quad form; below it is variant 3)
-    const int form = gemm_form(p, EPI, variant);
-    if (form < 0) return hipErrorInvalidValue;
-    if (form == 0 && variant != 2 && variant != 1) variant = 0;      // incl. the fallback of a >= 4 GiB operand from the 32-bit forms
-    if constexpr (EPI == EPI_RESID_RMS) {
-        // only the persistent kernels carry this epilogue (LDS-staged, needs the cross-wave row reduction)
-        const int nwg = tiles_m * tiles_n;
-        dim3 pgrid(nwg < PERSISTENT_WGS ? nwg : PERSISTENT_WGS);
-        if (variant == 5)
-            hipLaunchKernelGGL((gemm_bf16_pingpong<EPI>), pgrid, block, 0, stream, p);
-        else
-            hipLaunchKernelGGL((gemm_bf16_persistent<EPI>), pgrid, block, 0, stream, p);
-        return hipGetLastError();
-    } else
-    if (variant == 0 || (EPI == EPI_HEADS && p.S < 8 && variant != 1 && variant != 2))   // the staged epilogue steps rows by 8 within a sample
-        hipLaunchKernelGGL((gemm_bf16_kernel<EPI, 0>), grid, block, 0, stream, p);
-    else if (variant == 2)
-        hipLaunchKernelGGL((gemm_bf16_kernel<EPI, 2>), grid, block, 0, stream, p);
-    else if (form == 12) {
-        if constexpr (EPI == EPI_F32 || EPI == EPI_BF16) {
-            const int items = ((p.N + 127) / 128) * (p.batch > 0 ? p.batch : 1);
-            if (p.f16 == 1) hipLaunchKernelGGL((gemm_bf16_stream<EPI, 1>), dim3(items), dim3(256), 0, stream, p);
-            else if (p.f16 == 2) hipLaunchKernelGGL((gemm_bf16_stream<EPI, 2>), dim3(items), dim3(256), 0, stream, p);
-            else hipLaunchKernelGGL((gemm_bf16_stream<EPI>), dim3(items), dim3(256), 0, stream, p);
-        }
-    } else if (p.f16 != 0 && form == 3) {
-        // fp16 operands on the persistent 8-wave kernel (plain schedule, no touch): gemm_form let only EPI_BF16 / EPI_F32 through
-        if constexpr (EPI == EPI_F32 || EPI == EPI_BF16) {
-            const int nwg = tiles_m * tiles_n * (p.batch > 0 ? p.batch : 1);
-            dim3 pgrid(nwg < PERSISTENT_WGS ? nwg : PERSISTENT_WGS);
-            if (p.f16 == 1) hipLaunchKernelGGL((gemm_bf16_persistent<EPI, 0, 1>), pgrid, block, 0, stream, p);
-            else hipLaunchKernelGGL((gemm_bf16_persistent<EPI, 0, 2>), pgrid, block, 0, stream, p);
-        } else {
-            return hipErrorInvalidValue;
-        }
-    } else if (form == 10) {
-        // quad form (gemm_quad.inc): every bf16-result launch of a call site, WHATEVER its M -- the form's k-order differs from the
-        // 8-wave forms' in the last ulp, so a weight must not change form with the batch size (a pair's bits are batch-invariant)
-        if constexpr (EPI == EPI_BF16 || EPI == EPI_BF16_QGELU || EPI == EPI_BF16_GELU || EPI == EPI_GATED || EPI == EPI_HEADS) {
-            // Few-row launches (a caller that scores one or two pairs): the slim form, gemm_slim.inc -- same bits, so the switch is a function of the launch's shape
-            // that never shows in a score.  variant 10 = the quad kernel whatever the shape (tests, A/B).  (As 128-row blocks of the STREAM form the same launches
-            // were slower than the quad kernel: its 128 x 32 wave tiles are built to keep HBM busy, not the matrix pipe -- profiles/r6_call24_*.)
-            if (gemm_takes_slim(p, EPI, variant)) {
-                const dim3 sgrid(((p.M + 127) / 128) * (p.N / 128));
-                if (p.f16 == 2) {
-                    if constexpr (EPI == EPI_BF16 || EPI == EPI_GATED) hipLaunchKernelGGL((gemm_slim<EPI, 2>), sgrid, dim3(256), 0, stream, p);
-                } else if (p.f16 == 1) {
-                    if constexpr (EPI != EPI_GATED) hipLaunchKernelGGL((gemm_slim<EPI, 1>), sgrid, dim3(256), 0, stream, p);
-                } else {
-                    hipLaunchKernelGGL((gemm_slim<EPI, 0>), sgrid, dim3(256), 0, stream, p);
-                }
-                return hipGetLastError();
-            }
-            const int nwg = tiles_m * tiles_n;
-            const dim3 qgrid(nwg < VQS_QUAD_WGS ? nwg : VQS_QUAD_WGS);
-            if (p.f16 == 4) {
-                if constexpr (EPI == EPI_BF16) hipLaunchKernelGGL((gemm_f16bs_quad<EPI>), qgrid, dim3(256), 0, stream, p);
-                else return hipErrorInvalidValue;
-            } else if (p.f16 == 3) {
-                if constexpr (EPI != EPI_BF16_QGELU) hipLaunchKernelGGL((gemm_f16s_quad<EPI>), qgrid, dim3(256), 0, stream, p);
-                else return hipErrorInvalidValue;
-            } else if (p.f16 == 2) {
-                if constexpr (EPI == EPI_BF16 || EPI == EPI_GATED) hipLaunchKernelGGL((gemm_f16b_quad<EPI>), qgrid, dim3(256), 0, stream, p);
-                else return hipErrorInvalidValue;
-            } else if (p.f16) {
-                if constexpr (EPI != EPI_GATED) hipLaunchKernelGGL((gemm_f16_quad<EPI>), qgrid, dim3(256), 0, stream, p);
-                else return hipErrorInvalidValue;
-            } else {
-                hipLaunchKernelGGL((gemm_bf16_quad<EPI>), qgrid, dim3(256), 0, stream, p);
-            }
-        }
-    } else if (variant == 5 && EPI != EPI_F32_RESID) {
-        if constexpr (EPI != EPI_F32_RESID) {
-            const int nwg = tiles_m * tiles_n * (p.batch > 0 ? p.batch : 1);
-            dim3 pgrid(nwg < PERSISTENT_WGS ? nwg : PERSISTENT_WGS);
-            hipLaunchKernelGGL((gemm_bf16_pingpong<EPI>), pgrid, block, 0, stream, p);
-        }
-    } else {
-        if constexpr (EPI == EPI_F32_RESID) {
-            // the in-epilogue fp32 read-modify-write does not fit the persistent kernel's register budget (it
-            // spills); the engine's hot path uses EPI_F32 + a fused add in the following norm kernel instead
-            hipLaunchKernelGGL((gemm_bf16_kernel<EPI, 0>), grid, block, 0, stream, p);
-        } else {
-            const int nwg = tiles_m * tiles_n * (p.batch > 0 ? p.batch : 1);
-            dim3 pgrid(nwg < PERSISTENT_WGS ? nwg : PERSISTENT_WGS);
-            // L2 touch (see gemm_bf16_persistent): shapes whose A panel has at most two window columns of reuse (N <= 2048:
-            // ViT out_proj / fc2, T5 o / wo) stream A from HBM and gain 2-8 % from the prefetch; wider shapes re-read A
-            // from L2 / Infinity Cache and lose 1-3 % to the extra requests, so they keep the plain kernel.  Exception: the
-            // XXL wo GEMM (N = 4096, K = 10240) -- its 8-M-tile A panels (42 MB per XCD, 336 MB per chip) overflow the
-            // 256 MB Infinity Cache, so the re-reads come from HBM: +1.4 % with the touch (1 231 -> 1 248 TFLOP/s, A/B r2 call 21).
-            const int tm = l2_touch_mode();
-            const bool touch_ok = tm != 0 && p.batch <= 1 && nwg >= PERSISTENT_WGS && p.K >= 4 * BK;
-            const bool touch = touch_ok && (p.l2_touch == 1 || (p.l2_touch == 0 && (tm == 1 || p.N <= 2048 || (p.N <= 4096 && p.K >= 8192))));   // l2_touch: caller's override (1 on, 2 off)
-            // schedule by shape: the ViT qkv (K = 1024, 2048 < N <= 3072) is 0-1 % faster on the ping-pong schedule; with
-            // the touch the lock-step kernel wins on out_proj (+7 %).  All of them produce bitwise-identical results.
-            if (variant != 7 && !touch && p.K <= 1024 && p.N <= 3072 && p.batch <= 1 && nwg >= PERSISTENT_WGS)   // 7 = lock-step forced (lab)
-                hipLaunchKernelGGL((gemm_bf16_pingpong<EPI>), pgrid, block, 0, stream, p);
-            else if (touch && (tm == 1 || tm == 3))
-                hipLaunchKernelGGL((gemm_bf16_persistent<EPI, 1>), pgrid, block, 0, stream, p);
-            else if (touch)
-                hipLaunchKernelGGL((gemm_bf16_persistent<EPI, 2>), pgrid, block, 0, stream, p);
-            else
-                hipLaunchKernelGGL((gemm_bf16_persistent<EPI>), pgrid, block, 0, stream, p);
-        }
-    }
-    return hipGetLastError();
-}
-
-
-hipError_t launch_gemm(const GemmParams& p_in, int epilogue, int variant, hipStream_t stream) {
-    GemmParams p = p_in;
+// THE DISPATCH RULE: which kernel a launch takes, and with which grid.  Everything that decides it is in this function (the
+// eligibility predicates it calls sit next to their kernels' constants: quad_eligible_rt above, stream_eligible in gemm_stream.inc,
+// slim_eligible in gemm_slim.inc); launch_gemm below only instantiates what the plan names.
+//
+// Two families of bits.  The quad family (quad and slim kernels) sums in a different k-order from the 8-wave family (tile, persistent,
+// ping-pong and stream kernels), so which FAMILY a launch takes is a function of the variant, the epilogue and the weight's shape,
+// never of M: a pair's bits must not depend on its batch.  Inside a family every kernel produces the same bits, so the choice there
+// follows the launch's shape and the caller's hints freely.
+//   variant 0 / 2   one tile per workgroup (lock-step / ping-pong schedule): plain launches only (no batch, no row scale, no split
+//                   result, 64-lane heads, no fused residual + RMSNorm);
+//   variant 3       the library's rule: a quad call site (quad_eligible_rt) runs the quad family -- the slim kernel for the few-row
+//                   launches slim_eligible names, else the quad kernel; every other launch follows the 8-wave rule;
+//   variant 10      as 3 with the quad kernel whatever the shape, and never the stream form (tests, A/B);
+//   variant 11      the 8-wave rule for every launch (A/B against the quad family);
+//   variant 5       the persistent ping-pong kernel;
+//   1, 4, 6-9       lab forms of rounds 1-3 (register-staged, wave-specialised, wide, ring; in the git history only): refused.
+//                   Any other value runs the 8-wave rule without the stream form.
+//   a handle's launch (`handle`) with a batch follows the library rule whatever the handle's variant.
+// The 8-wave rule: the stream kernel where stream_eligible (few rows per entry, variants 3 and 11 only); else a persistent kernel,
+// lock-step or ping-pong and with or without the L2 touch by shape (below).  Two launches ignore the variant: EPI_HEADS with S < 8
+// (the staged epilogue steps rows by 8 within a sample) and EPI_F32_RESID run one tile per workgroup, and EPI_RESID_RMS exists in
+// the persistent kernels only (LDS-staged, needs the cross-wave row reduction): ping-pong under variant 5, else lock-step.
+// fp16 operands (GemmParams::f16) exist in the quad family for the 16-bit epilogues each type has, and -- types 1 and 2, variant 3,
+// plain bias-free fp32 / 16-bit results -- in the stream kernel and the plain persistent kernel (the decoder's cross-attention score
+// path); anything else is refused.
+// The persistent, ping-pong and stream kernels address a batch entry's operands with 32-bit byte offsets and refuse operands of 4 GiB
+// or more; a plain launch then falls back to the one-tile-per-workgroup kernel (64-bit pointers, same bits), anything else is
+// refused -- never a wrapped offset.
+bool gemm_plan(const GemmParams& p, int epilogue, int variant, GemmPlan* plan, bool handle) {
+    if (handle && p.batch > 1) variant = GEMM_V_LIBRARY;
+    if (epilogue < 0 || epilogue >= EPI_COUNT || p.f16 < GEMM_T_BF16 || p.f16 > GEMM_T_F16S_BF16) return false;
+    if (variant == 1 || variant == 4 || (variant >= 6 && variant <= 9)) return false;
+    // the variants that reach the persistent kernels' staged epilogue: batches, the generalised HEADS / GATED epilogues and the row scale live there only
+    const bool staged = variant == GEMM_V_LIBRARY || variant == GEMM_V_PINGPONG || variant == GEMM_V_QUAD || variant == GEMM_V_8WAVE;
     if (p.rope_cos != nullptr || p.rope_sin != nullptr) {     // rotary embedding in the epilogue: scaled fp16 family, head-major scatter of whole 128-lane heads only
-        if (!(p.rope_cos && p.rope_sin) || p.f16 != 3 || epilogue != EPI_HEADS || p.hd != 128 || (p.hd_src != 0 && p.hd_src != 128)) return hipErrorInvalidValue;
+        if (!(p.rope_cos && p.rope_sin) || p.f16 != GEMM_T_F16S || epilogue != EPI_HEADS || p.hd != 128 || (p.hd_src != 0 && p.hd_src != 128)) return false;
     }
-    resolve_tile_order(p, PERSISTENT_WGS);
-    if (variant == 1 || variant == 4 || variant == 6 || variant == 7 || variant == 8 || variant == 9) return hipErrorInvalidValue;     // lab-only forms (see the file header)
     // N: a lane stores 4 consecutive columns; fp32 output may have a ragged N if ldc leaves room for the overhang
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K % BK) != 0) return hipErrorInvalidValue;
-    if ((p.N % 8) != 0 && !(epilogue == EPI_F32 && p.ldc >= ((p.N + 3) & ~3) && p.bias == nullptr)) return hipErrorInvalidValue;
-    if (p.batch > 1 && ((variant != 3 && variant != 4 && variant != 5 && variant != 6 && variant != 7 && variant != 8 && variant != 9 && variant != 10 && variant != 11) || epilogue == EPI_HEADS || epilogue == EPI_F32_RESID)) return hipErrorInvalidValue;
-    if ((p.lda % 8) != 0 || (p.ldw % 8) != 0) return hipErrorInvalidValue;
-    if (p.split_off != 0 && (epilogue != EPI_BF16 || (p.split_off % 8) != 0)) return hipErrorInvalidValue;   // split-bf16 results: plain bf16 epilogue, staged form
-    if ((p.hd > 64 || p.inner_kv > 0 || p.Hkv > 0 || p.gate_act != 0 || (epilogue == EPI_GATED && p.bias != nullptr)) &&
-        variant != 3 && variant != 5 && variant != 6 && variant != 7 && variant != 8 && variant != 9 && variant != 10 && variant != 11)
-        return hipErrorInvalidValue;   // generalised HEADS / GATED epilogues live in the persistent kernels only
-    if (p.rowss_in != nullptr && (p.rowss_parts < 0 || (variant != 3 && variant != 5 && variant != 6 && variant != 7 && variant != 8 && variant != 9 && variant != 10 && variant != 11) || epilogue == EPI_F32_RESID))
-        return hipErrorInvalidValue;   // the row scale lives in the persistent kernels' staged epilogue only
+    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K % BK) != 0) return false;
+    if ((p.N % 8) != 0 && !(epilogue == EPI_F32 && p.ldc >= ((p.N + 3) & ~3) && p.bias == nullptr)) return false;
+    if (p.batch > 1 && (!staged || epilogue == EPI_HEADS || epilogue == EPI_F32_RESID)) return false;
+    if ((p.lda % 8) != 0 || (p.ldw % 8) != 0) return false;
+    if (p.split_off != 0 && (epilogue != EPI_BF16 || (p.split_off % 8) != 0)) return false;   // split-bf16 results: plain bf16 epilogue, staged form
+    if ((p.hd > 64 || p.inner_kv > 0 || p.Hkv > 0 || p.gate_act != 0 || (epilogue == EPI_GATED && p.bias != nullptr)) && !staged) return false;
+    if (p.rowss_in != nullptr && (p.rowss_parts < 0 || !staged || epilogue == EPI_F32_RESID)) return false;
+    if (epilogue == EPI_RESID_RMS && (!p.hres || !p.lnw || !p.rowss_out || p.batch > 1 || p.bias != nullptr || (p.ldh % 4) != 0 || (p.ldc % 4) != 0)) return false;
+
+    const int batch = p.batch > 0 ? p.batch : 1;
+    const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);      // of one batch entry
+    const int nwg = tiles * batch;
+    auto take = [&](int kernel, int grid, int block, int touch = 0) {
+        *plan = GemmPlan{kernel, touch, p.f16, grid, block};
+        return true;
+    };
+    auto persistent = [&](int kernel, int touch = 0) { return take(kernel, nwg < PERSISTENT_WGS ? nwg : PERSISTENT_WGS, 512, touch); };
+    auto stream = [&] { return take(GEMM_K_STREAM, ((p.N + 127) / 128) * batch, 256); };
+    // quad family (gemm_quad.inc): every bf16-result launch of a call site, WHATEVER its M.  Few-row launches (a caller that scores one or
+    // two pairs) take the slim form, gemm_slim.inc -- same bits, so that switch is a function of the launch's shape that never shows in a
+    // score.  (As 128-row blocks of the STREAM form the same launches were slower than the quad kernel: its 128 x 32 wave tiles are built
+    // to keep HBM busy, not the matrix pipe -- profiles/r6_call24_*.)
+    auto quad = [&] {
+        if (variant == GEMM_V_LIBRARY && !p.no_stream && slim_eligible(p, epilogue)) return take(GEMM_K_SLIM, ((p.M + 127) / 128) * (p.N / 128), 256);
+        return take(GEMM_K_QUAD, tiles < VQS_QUAD_WGS ? tiles : VQS_QUAD_WGS, 256);
+    };
+    const bool quad_site = (variant == GEMM_V_LIBRARY || variant == GEMM_V_QUAD) && quad_eligible_rt(p, epilogue);
+    const bool fit32 = (uint64_t)p.M * (uint64_t)p.lda * 2ull < (1ull << 32) && (uint64_t)p.N * (uint64_t)p.ldw * 2ull < (1ull << 32);
+
+    if (p.f16 != GEMM_T_BF16) {
+        if (quad_site) {      // every 16-bit-result linear of the vision towers, the projector, the Qwen row and -- option enc_fp16 -- the T5 encoder's attention side
+            const bool has = p.f16 == GEMM_T_F16S_BF16 ? epilogue == EPI_BF16
+                           : p.f16 == GEMM_T_F16S    ? epilogue != EPI_BF16_QGELU
+                           : p.f16 == GEMM_T_F16     ? epilogue != EPI_GATED
+                                                     : (epilogue == EPI_BF16 || epilogue == EPI_GATED);
+            return has && quad();
+        }
+        if (p.f16 >= GEMM_T_F16S || variant != GEMM_V_LIBRARY || !(epilogue == EPI_BF16 || epilogue == EPI_F32) || p.bias != nullptr || p.rowss_in != nullptr) return false;
+        if (p.f16 == GEMM_T_F16 && p.split_off != 0) return false;
+        if (stream_eligible(p, epilogue)) return stream();
+        return fit32 && persistent(GEMM_K_PERSISTENT);
+    }
+    if (epilogue == EPI_RESID_RMS) return fit32 && persistent(variant == GEMM_V_PINGPONG ? GEMM_K_PINGPONG : GEMM_K_PERSISTENT);
+    const bool plain = !(p.hd > 64 || p.hd_src > 0 || p.inner_kv > 0 || p.Hkv > 0 || p.gate_act != 0 || (epilogue == EPI_GATED && p.bias != nullptr) || p.rowss_in != nullptr ||
+                         p.split_off != 0) && p.batch <= 1;
+    auto tile = [&](int kernel = GEMM_K_TILE) { return plain && take(kernel, tiles, 512); };
+    if (variant == GEMM_V_TILE || variant == GEMM_V_TILE_PINGPONG) return tile(variant == GEMM_V_TILE ? GEMM_K_TILE : GEMM_K_TILE_PINGPONG);
+    if (epilogue == EPI_HEADS && p.S < 8) return tile();
+    if (quad_site) return quad();      // first: a quad call site stays quad for every M
+    if ((variant == GEMM_V_LIBRARY || variant == GEMM_V_8WAVE) && stream_eligible(p, epilogue)) return stream();      // bitwise the 8-wave forms (gemm_stream.inc)
+    if (epilogue == EPI_HEADS && p.hd_src > 0 && p.hd_src != (p.hd > 0 ? p.hd : 64)) return false;   // narrow heads in wide slots: quad form only
+    // EPI_F32_RESID: the in-epilogue fp32 read-modify-write does not fit the persistent kernel's register budget (it spills); the
+    // engine's hot path uses EPI_F32 + a fused add in the following norm kernel instead
+    if (epilogue == EPI_F32_RESID) return take(GEMM_K_TILE, tiles, 512);
+    if (!fit32) return tile();
+    if (variant == GEMM_V_PINGPONG) return persistent(GEMM_K_PINGPONG);
+    // L2 touch (see gemm_bf16_persistent): shapes whose A panel has at most two window columns of reuse (N <= 2048:
+    // ViT out_proj / fc2, T5 o / wo) stream A from HBM and gain 2-8 % from the prefetch; wider shapes re-read A
+    // from L2 / Infinity Cache and lose 1-3 % to the extra requests, so they keep the plain kernel.  Exception: the
+    // XXL wo GEMM (N = 4096, K = 10240) -- its 8-M-tile A panels (42 MB per XCD, 336 MB per chip) overflow the
+    // 256 MB Infinity Cache, so the re-reads come from HBM: +1.4 % with the touch (1 231 -> 1 248 TFLOP/s, A/B r2 call 21).
+    const bool big = p.batch <= 1 && nwg >= PERSISTENT_WGS;
+    const bool touch = big && p.K >= 4 * BK && (p.l2_touch == 1 || (p.l2_touch == 0 && (p.N <= 2048 || (p.N <= 4096 && p.K >= 8192))));   // l2_touch: caller's override (1 on, 2 off)
+    // schedule by shape: the ViT qkv (K = 1024, 2048 < N <= 3072) is 0-1 % faster on the ping-pong schedule; with
+    // the touch the lock-step kernel wins on out_proj (+7 %).  All of them produce bitwise-identical results.
+    if (big && !touch && p.K <= 1024 && p.N <= 3072) return persistent(GEMM_K_PINGPONG);
+    return persistent(GEMM_K_PERSISTENT, touch ? 2 : 0);
+}
+
+// Instantiates and launches the kernel the plan names: one line per kernel template (the engines' most frequent first), no decision.  `exists` is a constant that keeps the
+// (epilogue, type) pairs without a kernel from instantiating; gemm_plan never names one.
+#define VQS_LAUNCH_IF(exists, wanted, ...)                                \
+    if constexpr (exists)                                                 \
+        if (wanted) {                                                     \
+            hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, stream, p); \
+            return hipGetLastError();                                     \
+        }
+template <int EPI>
+static hipError_t launch_epi(const GemmParams& p, const GemmPlan& g, hipStream_t stream) {
+    const dim3 grid(g.grid), block(g.block);
+    const int k = g.kernel, t = g.type;
+    constexpr bool quad_epi = EPI == EPI_BF16 || EPI == EPI_BF16_QGELU || EPI == EPI_BF16_GELU || EPI == EPI_GATED || EPI == EPI_HEADS;
+    constexpr bool plain_epi = EPI == EPI_BF16 || EPI == EPI_F32, has_f16b = EPI == EPI_BF16 || EPI == EPI_GATED, has_f16 = quad_epi && EPI != EPI_GATED;
+    VQS_LAUNCH_IF(quad_epi, k == GEMM_K_QUAD && t == GEMM_T_BF16, gemm_bf16_quad<EPI>)
+    VQS_LAUNCH_IF(has_f16, k == GEMM_K_QUAD && t == GEMM_T_F16, gemm_f16_quad<EPI>)
+    VQS_LAUNCH_IF(has_f16b, k == GEMM_K_QUAD && t == GEMM_T_F16_BF16, gemm_f16b_quad<EPI>)
+    VQS_LAUNCH_IF(quad_epi && EPI != EPI_BF16_QGELU, k == GEMM_K_QUAD && t == GEMM_T_F16S, gemm_f16s_quad<EPI>)
+    VQS_LAUNCH_IF(EPI == EPI_BF16, k == GEMM_K_QUAD && t == GEMM_T_F16S_BF16, gemm_f16bs_quad<EPI>)
+    VQS_LAUNCH_IF(quad_epi, k == GEMM_K_SLIM && t == GEMM_T_BF16, gemm_slim<EPI, 0>)
+    VQS_LAUNCH_IF(has_f16, k == GEMM_K_SLIM && t == GEMM_T_F16, gemm_slim<EPI, 1>)
+    VQS_LAUNCH_IF(has_f16b, k == GEMM_K_SLIM && t == GEMM_T_F16_BF16, gemm_slim<EPI, 2>)
+    VQS_LAUNCH_IF(EPI != EPI_F32_RESID, k == GEMM_K_PERSISTENT && t == GEMM_T_BF16 && g.touch == 0, gemm_bf16_persistent<EPI>)
+    VQS_LAUNCH_IF(EPI != EPI_F32_RESID && EPI != EPI_RESID_RMS, k == GEMM_K_PERSISTENT && t == GEMM_T_BF16 && g.touch == 2, gemm_bf16_persistent<EPI, 2>)
+    VQS_LAUNCH_IF(plain_epi, k == GEMM_K_PERSISTENT && t == GEMM_T_F16, gemm_bf16_persistent<EPI, 0, 1>)
+    VQS_LAUNCH_IF(plain_epi, k == GEMM_K_PERSISTENT && t == GEMM_T_F16_BF16, gemm_bf16_persistent<EPI, 0, 2>)
+    VQS_LAUNCH_IF(plain_epi, k == GEMM_K_STREAM && t == GEMM_T_BF16, gemm_bf16_stream<EPI>)
+    VQS_LAUNCH_IF(plain_epi, k == GEMM_K_STREAM && t == GEMM_T_F16, gemm_bf16_stream<EPI, 1>)
+    VQS_LAUNCH_IF(plain_epi, k == GEMM_K_STREAM && t == GEMM_T_F16_BF16, gemm_bf16_stream<EPI, 2>)
+    VQS_LAUNCH_IF(EPI != EPI_RESID_RMS, k == GEMM_K_TILE, gemm_bf16_kernel<EPI, 0>)
+    VQS_LAUNCH_IF(EPI != EPI_RESID_RMS, k == GEMM_K_TILE_PINGPONG, gemm_bf16_kernel<EPI, 2>)
+    VQS_LAUNCH_IF(EPI != EPI_F32_RESID, k == GEMM_K_PINGPONG, gemm_bf16_pingpong<EPI>)
+    return hipErrorInvalidValue;      // a plan without a kernel
+}
+#undef VQS_LAUNCH_IF
+
+hipError_t launch_gemm(const GemmParams& p_in, int epilogue, int variant, hipStream_t stream, bool handle) {
+    GemmParams p = p_in;
+    resolve_tile_order(p, PERSISTENT_WGS);
+    GemmPlan g;
+    if (!gemm_plan(p, epilogue, variant, &g, handle)) return hipErrorInvalidValue;
     switch (epilogue) {
-        case EPI_BF16: return launch_epi<EPI_BF16>(p, variant, stream);
-        case EPI_BF16_QGELU: return launch_epi<EPI_BF16_QGELU>(p, variant, stream);
-        case EPI_BF16_GELU: return launch_epi<EPI_BF16_GELU>(p, variant, stream);
-        case EPI_F32: return launch_epi<EPI_F32>(p, variant, stream);
-        case EPI_F32_RESID: return launch_epi<EPI_F32_RESID>(p, variant, stream);
-        case EPI_GATED: return launch_epi<EPI_GATED>(p, variant, stream);
-        case EPI_HEADS: return launch_epi<EPI_HEADS>(p, variant, stream);
-        case EPI_RESID_RMS:
-            if (!p.hres || !p.lnw || !p.rowss_out || p.batch > 1 || p.bias != nullptr || (p.ldh % 4) != 0 || (p.ldc % 4) != 0)
-                return hipErrorInvalidValue;
-            return launch_epi<EPI_RESID_RMS>(p, variant, stream);
-        default: return hipErrorInvalidValue;
+        case EPI_BF16: return launch_epi<EPI_BF16>(p, g, stream);
+        case EPI_BF16_QGELU: return launch_epi<EPI_BF16_QGELU>(p, g, stream);
+        case EPI_BF16_GELU: return launch_epi<EPI_BF16_GELU>(p, g, stream);
+        case EPI_F32: return launch_epi<EPI_F32>(p, g, stream);
+        case EPI_F32_RESID: return launch_epi<EPI_F32_RESID>(p, g, stream);
+        case EPI_GATED: return launch_epi<EPI_GATED>(p, g, stream);
+        case EPI_HEADS: return launch_epi<EPI_HEADS>(p, g, stream);
+        default: return launch_epi<EPI_RESID_RMS>(p, g, stream);
     }
 }
 

@@ -44,7 +44,7 @@
 // M, N, the tile order or the position of the row in the batch: a pair's bits do not depend on the batch it is scored in
 // (tests/test_gpu_bench_config.py).  A 16x16x32 MFMA adds a k-step's 32 products in the order two 32x32x16 MFMAs do, so the
 // 8-wave forms produce the SAME bits (test_gemm_quad_form_is_bitwise_the_other_forms: torch.equal against variant 0 and 11 on
-// every epilogue); every bf16-result call site still runs THIS form for every M (launch_epi) -- the guarantee then does not
+// every epilogue); every bf16-result call site still runs THIS form for every M (gemm_plan) -- the guarantee then does not
 // rest on that hardware property -- and the others keep the fp32-result / batched / tiny-K launches.
 // =====================================================================================================
 #ifndef VQS_QUAD_ORDER

@@ -16,7 +16,7 @@
 // Numerics: v_mfma_f32_32x32x16_bf16 with the W fragment as the A operand, k ascending in steps of 16, one accumulator chain per
 // output element -- operand roles, k-slot mapping and order of gemm_bf16_kernel / gemm_bf16_persistent: results are BITWISE those
 // of the 8-wave forms (tests/test_gpu_kernels.py holds it against variant 0), so which launches take this form (a function of M,
-// N and the batch count, gemm_form) never shows in a pair's bits.
+// N and the batch count, gemm_plan) never shows in a pair's bits.
 // =====================================================================================================
 static constexpr int ST_STAGES = 5;
 static constexpr int ST_PD = ST_STAGES - 1;                 // slabs issued ahead of the one computed

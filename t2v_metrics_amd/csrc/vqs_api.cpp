@@ -303,12 +303,33 @@ int vqs_debug_tap_window(vqs_handle* h, int32_t first, int32_t count) {
 
 int vqs_debug_gemm_form(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t epilogue, int32_t batch, int32_t variant,
                         int32_t S, int32_t inner, int32_t inner_kv) {
-    if (M <= 0 || N <= 0 || K <= 0 || epilogue < 0 || epilogue >= vqs::EPI_COUNT) return -1;
+    const int32_t launch[VQS_GEMM_PLAN_FIELDS] = {M, N, K, lda, ldw, N, epilogue, batch > 0 ? batch : 1, variant & 0xff, S, inner, inner_kv};
+    int32_t plan[5];
+    if (vqs_debug_gemm_plan(launch, VQS_GEMM_PLAN_FIELDS, plan) != 1) return -1;
+    static const int form_of[] = {0, 0, 3, 3, 12, 10, 13};      // by vqs::GemmKernel: tile, tile ping-pong, persistent, ping-pong, stream, quad, slim
+    return form_of[plan[0]];
+}
+
+int vqs_debug_gemm_plan(const int32_t* launch, int32_t n, int32_t* plan) {
+    if (!launch || n != VQS_GEMM_PLAN_FIELDS || !plan) return VQS_ERR_INVALID;
+    static const float present = 0.0f;      // stands for an operand that is there: the plan is host arithmetic and reads no operand
+    enum { F_BIAS = 1, F_ROWSS = 2, F_NO_STREAM = 4, F_ROPE_COS = 8, F_ROPE_SIN = 16, F_RMS = 32, F_HANDLE = 64 };
+    const int32_t flags = launch[18];
     vqs::GemmParams p{};
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = N; p.batch = batch > 0 ? batch : 1;
-    p.S = S; p.inner = inner; p.inner_kv = inner_kv;
-    const int form = vqs::gemm_form(p, epilogue, variant & 0xff);
-    return (form == 10 && vqs::gemm_takes_slim(p, epilogue, variant & 0xff)) ? 13 : form;      // 13: a quad call site's few-row launch (gemm_slim.inc, same bits)
+    p.M = launch[0]; p.N = launch[1]; p.K = launch[2]; p.lda = launch[3]; p.ldw = launch[4]; p.ldc = launch[5]; p.batch = launch[7];
+    p.S = launch[9]; p.inner = launch[10]; p.inner_kv = launch[11]; p.hd = launch[12]; p.hd_src = launch[13]; p.Hkv = launch[14];
+    p.f16 = launch[15]; p.l2_touch = launch[16]; p.split_off = launch[17];
+    p.gate_act = launch[19]; p.rowss_parts = launch[20]; p.ldh = launch[21];
+    if (flags & F_BIAS) p.bias = (const bf16_t*)&present;
+    if (flags & F_ROWSS) p.rowss_in = &present;
+    if (flags & F_NO_STREAM) p.no_stream = 1;
+    if (flags & F_ROPE_COS) p.rope_cos = &present;
+    if (flags & F_ROPE_SIN) p.rope_sin = &present;
+    if (flags & F_RMS) { p.hres = const_cast<float*>(&present); p.lnw = (const bf16_t*)&present; p.rowss_out = const_cast<float*>(&present); }
+    vqs::GemmPlan g;
+    if (!vqs::gemm_plan(p, launch[6], launch[8] & 0xff, &g, (flags & F_HANDLE) != 0)) return 0;
+    plan[0] = g.kernel; plan[1] = g.touch; plan[2] = g.type; plan[3] = g.grid; plan[4] = g.block;
+    return 1;
 }
 
 int vqs_debug_gemm_batched(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldc,
@@ -718,7 +739,7 @@ static int encoder_pass(vqs_handle* h, const ScoreWs& w, const void* d_feats, co
     // the consuming qkv / wi GEMM scales its accumulator rows by 1/rms.  Bit-exact repeatable and parity-tested, but the
     // read-modify-write epilogue costs the producer GEMMs +0.55 ms per launch against 0.64 ms for the norm kernel it
     // removes (+1 % end to end, and it lowers the GEMM's own roofline fraction): kept as a lab path.
-    const bool fused = h->fused_norm != 0 && (h->gemm_variant == 3 || h->gemm_variant == 11 || h->gemm_variant == 5 || h->gemm_variant == 7);   // the fused epilogue's launches are not quad-eligible: they run the 8-wave forms
+    const bool fused = h->fused_norm != 0 && (h->gemm_variant == 3 || h->gemm_variant == 11 || h->gemm_variant == 5);   // the fused epilogue's launches are not quad-eligible: they run the 8-wave forms
     const int parts = (D + 255) / 256;
     bool scaled = false;          // w.xn holds an un-normalised operand whose row sums are in w.rowss
     const bf16_t* pend = nullptr;
@@ -1251,7 +1272,7 @@ int vqs_profile_bytes(vqs_handle* h, double* gemm_bytes) {
 
 // ---------------------------------------------------------------------------- single-kernel entry points
 // GEMM with the fused residual + RMSNorm pieces (tests): epilogue 7 (producer: hres/lnw/rowss_out) and/or a consumer row
-// scale (rowss_in/rowss_parts/rs_invd/rs_eps) in front of epilogues 0, 3, 5, 6.  Persistent variants (3, 5, 7) only.
+// scale (rowss_in/rowss_parts/rs_invd/rs_eps) in front of epilogues 0, 3, 5, 6.  Variants 3, 5, 10 and 11 only.
 int vqs_gemm_rms(const void* A, const void* W, void* C, float* hres, const void* lnw, float* rowss_out, const float* rowss_in,
                  int32_t rowss_parts, float rs_invd, float rs_eps, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw,
                  int32_t ldc, int32_t epilogue, int32_t S, int32_t H, int32_t variant, void* stream) {

@@ -160,7 +160,7 @@ struct GemmCall {
 
 // What the handle decides about a launch (all but `variant` bitwise-neutral): the defaults are what the Qwen and CLIPScore handles run.
 struct GemmOpts {
-    int variant = 3;           // kernel form of unbatched launches (option gemm_variant); batched ones always run the persistent kernel
+    int variant = 3;           // option gemm_variant (GemmVariant; what it selects: gemm.hip gemm_plan)
     bool stream = true;        // option stream_gemm
     int tile_gm = 0, tile_ns = 0, l2_touch = 0;
     int nt_store = -1;         // -1: the call site's choice
@@ -198,7 +198,7 @@ inline int run_gemm(HostBase* h, const GemmCall& g, const GemmOpts& o, hipStream
         }
         VQS_HIP(h, hipEventRecord(pr.ev[pr.used], st), "hipEventRecord");
     }
-    VQS_HIP(h, launch_gemm(p, g.epi, g.batch > 1 ? 3 : o.variant, st), std::string("gemm ") + what);
+    VQS_HIP(h, launch_gemm(p, g.epi, o.variant, st, true), std::string("gemm ") + what);
     if (pr.on) {
         VQS_HIP(h, hipEventRecord(pr.ev[pr.used + 1], st), "hipEventRecord");
         pr.used += 2;

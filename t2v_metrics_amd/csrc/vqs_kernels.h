@@ -177,10 +177,43 @@ inline void resolve_tile_order(GemmParams& p, int persistent_wgs) {
 }
 
 
-// variant 0 = direct-to-LDS (global_load_lds) staging; variant 1 = register-staged (debug / A-B)
-int gemm_form(const GemmParams& p, int epilogue, int variant);   // kernel family a launch resolves to (gemm.hip), host arithmetic
-bool gemm_takes_slim(const GemmParams& p, int epilogue, int variant);   // a quad call site (form 10) whose launch runs the few-row slim form (gemm_slim.inc: same bits)
-hipError_t launch_gemm(const GemmParams& p, int epilogue, int variant, hipStream_t stream);
+// The numbers below are C ABI (vqs_gemm's variant word, option gemm_variant, the test hooks); the rule that turns them into a kernel is
+// stated once, at gemm_plan (gemm.hip).
+enum GemmVariant : int {       // bits 0-7 of the variant word; 1, 4 and 6-9 were lab forms and are refused
+    GEMM_V_TILE = 0,           // one tile per workgroup
+    GEMM_V_TILE_PINGPONG = 2,  // one tile per workgroup, ping-pong schedule
+    GEMM_V_LIBRARY = 3,        // the library's rule: quad call sites on the quad family, everything else on the 8-wave rule
+    GEMM_V_PINGPONG = 5,       // the persistent ping-pong kernel
+    GEMM_V_QUAD = 10,          // as 3, with the quad kernel itself whatever the shape (never slim, never stream)
+    GEMM_V_8WAVE = 11          // the 8-wave rule for every launch
+};
+enum GemmOperands : int {      // GemmParams::f16
+    GEMM_T_BF16 = 0,           // bf16 operands and result
+    GEMM_T_F16 = 1,            // fp16 operands and result
+    GEMM_T_F16_BF16 = 2,       // fp16 operands, bf16 result
+    GEMM_T_F16S = 3,           // as 1 behind the power-of-two scales acc_scale / out_scale
+    GEMM_T_F16S_BF16 = 4       // as 2 behind the scales
+};
+enum GemmKernel : int {        // kernel family of a plan
+    GEMM_K_TILE = 0,           // gemm_bf16_kernel<EPI, 0>
+    GEMM_K_TILE_PINGPONG,      // gemm_bf16_kernel<EPI, 2>
+    GEMM_K_PERSISTENT,         // gemm_bf16_persistent<EPI, touch, type>
+    GEMM_K_PINGPONG,           // gemm_bf16_pingpong<EPI>
+    GEMM_K_STREAM,             // gemm_bf16_stream<EPI, type>
+    GEMM_K_QUAD,               // gemm_bf16_quad / gemm_f16_quad / gemm_f16b_quad / gemm_f16s_quad / gemm_f16bs_quad <EPI>, by type
+    GEMM_K_SLIM                // gemm_slim<EPI, type>
+};
+struct GemmPlan {
+    int kernel;                // GemmKernel
+    int touch;                 // GEMM_K_PERSISTENT: its TOUCH parameter, 0 or 2 (L2 prefetch of the A panel)
+    int type;                  // GemmOperands the kernel is instantiated for
+    int grid, block;           // workgroups, threads per workgroup
+};
+// The kernel a launch takes, or false where launch_gemm answers hipErrorInvalidValue.  Host arithmetic only.  handle: a launch of one of the
+// engine handles (vqs_host.h run_gemm), whose variant is the handle's option gemm_variant: its batched launches follow the library rule
+// whatever that option says, since only the 8-wave and stream kernels take a batch.
+bool gemm_plan(const GemmParams& p, int epilogue, int variant, GemmPlan* plan, bool handle = false);
+hipError_t launch_gemm(const GemmParams& p, int epilogue, int variant, hipStream_t stream, bool handle = false);
 
 // ---------------------------------------------------------------- attention (attn.hip)
 struct AttnParams {

@@ -42,6 +42,20 @@ int main() {
     assert(vqs_debug_gemm_form(128, 608, 4096, 4096, 4096, 3, 256, 3, 0, 0, 0) == 12 && vqs_debug_gemm_form(128, 608, 4096, 4096, 4096, 3, 16, 3, 0, 0, 0) == 12 &&
            vqs_debug_gemm_form(64, 384, 4096, 4096, 4096, 3, 1, 3, 0, 0, 0) == 3);
     assert(vqs_debug_gemm_form(64, 32768, 4096, 4096, 4096, 0, 1, 3, 0, 0, 0) == 13 && vqs_debug_gemm_form(64, 32768, 4096, 4096, 4096, 0, 1, 10, 0, 0, 0) == 10);
+    {   // the whole plan behind those numbers (gemm.hip gemm_plan): kernel family, touch, operand type, workgroups, workgroup size
+        int32_t l[VQS_GEMM_PLAN_FIELDS] = {8192, 2048, 256, 256, 256, 2048, 3, 1, 3, 1, 1}, g[5] = {-1, -1, -1, -1, -1};
+        assert(vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS, g) == 1 && g[0] == 2 && g[1] == 2 && g[2] == 0 && g[3] == 256 && g[4] == 512);   // lock-step with the L2 touch
+        l[16] = 2;                                                                                                                            // touch off: ping-pong
+        assert(vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS, g) == 1 && g[0] == 3 && g[1] == 0 && g[3] == 256 && g[4] == 512);
+        l[8] = 7;                                                                                                                             // a lab variant: refused
+        assert(vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS, g) == 0);
+        l[8] = 3; l[6] = 7;                                                                                                                   // epilogue 7 without / with its operands
+        assert(vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS, g) == 0);
+        l[18] = 32; l[21] = 2048;
+        assert(vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS, g) == 1 && g[0] == 2 && g[1] == 0 && g[3] == 256);
+        assert(vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS - 1, g) == VQS_ERR_INVALID && vqs_debug_gemm_plan(nullptr, VQS_GEMM_PLAN_FIELDS, g) == VQS_ERR_INVALID &&
+               vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS, nullptr) == VQS_ERR_INVALID);
+    }
     assert(vqs_debug_gemm_batched(nullptr, nullptr, nullptr, 128, 608, 4096, 4096, 4096, 640, 3, 256, 0, 0, 0, 0, 0, 3, nullptr) == VQS_ERR_INVALID);
     {
         int dummy2 = 0;
