@@ -1,6 +1,7 @@
 /* vqs_debug.h -- test hooks and lab switches of libvqs_hip.so.  NOT part of the drop-in boundary (include/vqs.h): nothing the
  * reference-side binding of INTEGRATION.md needs is declared here.  The parity tests (tests/test_gpu_stage_locked.py,
- * tests/test_gpu_bench_config.py, tests/test_properties.py) and the lab tools (tools/lab_call.py) are the only callers. */
+ * tests/test_gpu_bench_config.py, tests/test_properties.py) and the lab tools (tools/lab_call.py) are the only callers.
+ * vqs_debug_gemm_launch: single launches of the GEMM's Qwen2.5-VL epilogues (tests/test_gpu_gemm_epilogues.py, profiles/gemm_epilogue_kernels.md). */
 #ifndef VQS_DEBUG_H
 #define VQS_DEBUG_H
 #include "vqs.h"
@@ -48,6 +49,21 @@ int vqs_debug_gemm_form(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ld
  * threads per workgroup; 0 where the launcher refuses the launch (hipErrorInvalidValue); VQS_ERR_INVALID for a bad call of the hook. */
 #define VQS_GEMM_PLAN_FIELDS 22
 int vqs_debug_gemm_plan(const int32_t* launch, int32_t n, int32_t* plan);
+/* Device-side test hook: ONE launch of the GEMM with every field of its parameter block in the caller's hands (the Qwen2.5-VL row's epilogues: 128-lane
+ * heads, narrow heads in wide slots, the grouped-query scatter, the SiLU gate and the gated bias, the scaled fp16 families, the rotary embedding inside the
+ * head-major epilogue -- tests/test_gpu_gemm_epilogues.py).  It fills the block by the function vqs_debug_gemm_plan fills it with and calls launch_gemm,
+ * nothing else: no copy, no synchronisation.
+ *   launch[VQS_GEMM_LAUNCH_FIELDS]: the VQS_GEMM_PLAN_FIELDS integers above, then 22 H (heads of the q tensor: EPI_HEADS, > 0 there).  The first 22 given to
+ *     vqs_debug_gemm_plan name the kernel this launch runs.  A flag that is set requires its pointer below, and a pointer without its flag is an error.
+ *   ptrs[VQS_GEMM_LAUNCH_PTRS]: 0 A, 1 W, 2 C (every epilogue but EPI_HEADS), 3 bias (bf16 [N]; gated: packed column order), 4-6 heads_out[0..2] (EPI_HEADS:
+ *     q [B, H, S, hd], k and v [B, Hkv, S, hd]), 7 rope_cos, 8 rope_sin (fp32 [M, 64]), 9 rowss_in (fp32 [rowss_parts][M]); unused ones NULL.
+ *   scales[VQS_GEMM_LAUNCH_SCALES]: 0 acc_scale, 1 out_scale (operand types 3 and 4; 1 otherwise), 2 rs_invd, 3 rs_eps (row scale).
+ * A launch the launcher refuses returns VQS_ERR_INVALID and nothing is launched; so does a bad call of the hook.  Batched launches (batch > 1), EPI_RESID_RMS,
+ * EPI_F32_RESID, split results and the handle flag stay with vqs_debug_gemm_batched / vqs_gemm_rms / vqs_gemm: VQS_ERR_INVALID here. */
+#define VQS_GEMM_LAUNCH_FIELDS 23
+#define VQS_GEMM_LAUNCH_PTRS 10
+#define VQS_GEMM_LAUNCH_SCALES 4
+int vqs_debug_gemm_launch(const int32_t* launch, int32_t n, const void* const* ptrs, int32_t nptrs, const float* scales, int32_t nscales, void* stream);
 /* Device-side test hook: the batched form of vqs_gemm that the engine's decoder launches (entry z reads A + z*sA, W + z*sW and
  * writes C + z*sC, strides in elements; EPI_F32 or EPI_BF16 only), with the split-bf16 result store (split_off != 0: the lo plane
  * bf16(acc - hi) goes to C + split_off) and no_stream = 1 keeping the launch off the stream form (csrc/gemm_stream.inc).  The

@@ -284,6 +284,30 @@ struct VitBlocksCtx {
     int tap(int layer, const char* what, const void* p, size_t bytes) { return vqs::tap(h, "vit", layer, what, p, bytes, st); }
 };
 
+// The integers of a GEMM launch (include/vqs_debug.h, VQS_GEMM_PLAN_FIELDS) as the launcher's parameter block: the ONE place both GEMM hooks fill it, so that
+// vqs_debug_gemm_plan describes exactly what vqs_debug_gemm_launch launches.  An operand whose flag is set is taken from `ops`; everything else stays null.
+enum { GL_BIAS = 1, GL_ROWSS = 2, GL_NO_STREAM = 4, GL_ROPE_COS = 8, GL_ROPE_SIN = 16, GL_RMS = 32, GL_HANDLE = 64 };
+struct GemmLaunchOperands {
+    const void* bias;
+    const float *rowss_in, *rope_cos, *rope_sin;
+    float* hres;
+    const bf16_t* lnw;
+    float* rowss_out;
+};
+void gemm_params_of(const int32_t* launch, const GemmLaunchOperands& ops, vqs::GemmParams& p) {
+    const int32_t flags = launch[18];
+    p.M = launch[0]; p.N = launch[1]; p.K = launch[2]; p.lda = launch[3]; p.ldw = launch[4]; p.ldc = launch[5]; p.batch = launch[7];
+    p.S = launch[9]; p.inner = launch[10]; p.inner_kv = launch[11]; p.hd = launch[12]; p.hd_src = launch[13]; p.Hkv = launch[14];
+    p.f16 = launch[15]; p.l2_touch = launch[16]; p.split_off = launch[17];
+    p.gate_act = launch[19]; p.rowss_parts = launch[20]; p.ldh = launch[21];
+    if (flags & GL_BIAS) p.bias = (const bf16_t*)ops.bias;
+    if (flags & GL_ROWSS) p.rowss_in = ops.rowss_in;
+    if (flags & GL_NO_STREAM) p.no_stream = 1;
+    if (flags & GL_ROPE_COS) p.rope_cos = ops.rope_cos;
+    if (flags & GL_ROPE_SIN) p.rope_sin = ops.rope_sin;
+    if (flags & GL_RMS) { p.hres = ops.hres; p.lnw = ops.lnw; p.rowss_out = ops.rowss_out; }
+}
+
 }  // namespace
 
 extern "C" {
@@ -313,23 +337,38 @@ int vqs_debug_gemm_form(int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ld
 int vqs_debug_gemm_plan(const int32_t* launch, int32_t n, int32_t* plan) {
     if (!launch || n != VQS_GEMM_PLAN_FIELDS || !plan) return VQS_ERR_INVALID;
     static const float present = 0.0f;      // stands for an operand that is there: the plan is host arithmetic and reads no operand
-    enum { F_BIAS = 1, F_ROWSS = 2, F_NO_STREAM = 4, F_ROPE_COS = 8, F_ROPE_SIN = 16, F_RMS = 32, F_HANDLE = 64 };
-    const int32_t flags = launch[18];
+    float* const there = const_cast<float*>(&present);
+    const GemmLaunchOperands ops{there, there, there, there, there, (const bf16_t*)there, there};
     vqs::GemmParams p{};
-    p.M = launch[0]; p.N = launch[1]; p.K = launch[2]; p.lda = launch[3]; p.ldw = launch[4]; p.ldc = launch[5]; p.batch = launch[7];
-    p.S = launch[9]; p.inner = launch[10]; p.inner_kv = launch[11]; p.hd = launch[12]; p.hd_src = launch[13]; p.Hkv = launch[14];
-    p.f16 = launch[15]; p.l2_touch = launch[16]; p.split_off = launch[17];
-    p.gate_act = launch[19]; p.rowss_parts = launch[20]; p.ldh = launch[21];
-    if (flags & F_BIAS) p.bias = (const bf16_t*)&present;
-    if (flags & F_ROWSS) p.rowss_in = &present;
-    if (flags & F_NO_STREAM) p.no_stream = 1;
-    if (flags & F_ROPE_COS) p.rope_cos = &present;
-    if (flags & F_ROPE_SIN) p.rope_sin = &present;
-    if (flags & F_RMS) { p.hres = const_cast<float*>(&present); p.lnw = (const bf16_t*)&present; p.rowss_out = const_cast<float*>(&present); }
+    gemm_params_of(launch, ops, p);
     vqs::GemmPlan g;
-    if (!vqs::gemm_plan(p, launch[6], launch[8] & 0xff, &g, (flags & F_HANDLE) != 0)) return 0;
+    if (!vqs::gemm_plan(p, launch[6], launch[8] & 0xff, &g, (launch[18] & GL_HANDLE) != 0)) return 0;
     plan[0] = g.kernel; plan[1] = g.touch; plan[2] = g.type; plan[3] = g.grid; plan[4] = g.block;
     return 1;
+}
+
+int vqs_debug_gemm_launch(const int32_t* launch, int32_t n, const void* const* ptrs, int32_t nptrs, const float* scales, int32_t nscales, void* stream) {
+    if (!launch || n != VQS_GEMM_LAUNCH_FIELDS || !ptrs || nptrs != VQS_GEMM_LAUNCH_PTRS || !scales || nscales != VQS_GEMM_LAUNCH_SCALES) return VQS_ERR_INVALID;
+    enum { P_A, P_W, P_C, P_BIAS, P_HEADS0, P_HEADS1, P_HEADS2, P_ROPE_COS, P_ROPE_SIN, P_ROWSS };
+    const int32_t flags = launch[18], epilogue = launch[6];
+    // batched launches, the fused residual + RMSNorm, split results and a handle's launches have hooks of their own (vqs_debug_gemm_batched, vqs_gemm_rms);
+    // EPI_F32_RESID's residual is not among ptrs
+    if (launch[7] > 1 || epilogue == vqs::EPI_RESID_RMS || epilogue == vqs::EPI_F32_RESID || launch[17] != 0 || (flags & ~(GL_BIAS | GL_ROWSS | GL_NO_STREAM | GL_ROPE_COS | GL_ROPE_SIN)) != 0)
+        return VQS_ERR_INVALID;
+    // a flag requires its pointer and a pointer its flag: the plan hook, which sees the flags only, then describes this very launch
+    const struct { int flag, ptr; } pairs[] = {{GL_BIAS, P_BIAS}, {GL_ROWSS, P_ROWSS}, {GL_ROPE_COS, P_ROPE_COS}, {GL_ROPE_SIN, P_ROPE_SIN}};
+    for (const auto& pr : pairs)
+        if (((flags & pr.flag) != 0) != (ptrs[pr.ptr] != nullptr)) return VQS_ERR_INVALID;
+    if (!ptrs[P_A] || !ptrs[P_W]) return VQS_ERR_INVALID;
+    if (epilogue == vqs::EPI_HEADS ? (!ptrs[P_HEADS0] || !ptrs[P_HEADS1] || !ptrs[P_HEADS2] || launch[22] <= 0 || launch[9] <= 0) : !ptrs[P_C]) return VQS_ERR_INVALID;
+    const GemmLaunchOperands ops{ptrs[P_BIAS], (const float*)ptrs[P_ROWSS], (const float*)ptrs[P_ROPE_COS], (const float*)ptrs[P_ROPE_SIN], nullptr, nullptr, nullptr};
+    vqs::GemmParams p{};
+    gemm_params_of(launch, ops, p);
+    p.A = (const bf16_t*)ptrs[P_A]; p.W = (const bf16_t*)ptrs[P_W]; p.C = const_cast<void*>(ptrs[P_C]);
+    for (int t = 0; t < 3; ++t) p.heads_out[t] = (bf16_t*)const_cast<void*>(ptrs[P_HEADS0 + t]);
+    p.H = launch[22];
+    p.acc_scale = scales[0]; p.out_scale = scales[1]; p.rs_invd = scales[2]; p.rs_eps = scales[3];
+    return vqs::abi_code(vqs::launch_gemm(p, epilogue, launch[8] & 0xff, (hipStream_t)stream));
 }
 
 int vqs_debug_gemm_batched(const void* A, const void* W, void* C, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldc,

@@ -102,6 +102,7 @@ _SIGNATURES = {
     "vqs_debug_gemm_form": (_c_i32, [_c_i32] * 11),
     "vqs_debug_gemm_plan": (_c_i32, [_c_vp, _c_i32, _c_vp]),
     "vqs_debug_gemm_batched": (_c_i32, [_c_vp, _c_vp, _c_vp] + [_c_i32] * 8 + [_c_i64] * 4 + [_c_i32, _c_i32, _c_vp]),
+    "vqs_debug_gemm_launch": (_c_i32, [_c_vp, _c_i32, _c_vp, _c_i32, _c_vp, _c_i32, _c_vp]),
     "vqs_debug_heads_rows": (_c_i32, [_c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_vp]),
     "vqs_debug_tile_order": (_c_i32, [_c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, _c_vp]),
     "vqs_relpos_bucket": (_c_i32, [_c_i32, _c_i32, _c_i32, _c_i32]),
@@ -588,6 +589,26 @@ def gemm_batched(A, W, epilogue: int, split: bool = False, no_stream: bool = Fal
     if rc != 0:
         raise VqsError(f"vqs_debug_gemm_batched failed ({rc})")
     return (out[0], out[1]) if split else out[0]
+
+
+GEMM_LAUNCH_FIELDS = ("M", "N", "K", "lda", "ldw", "ldc", "epi", "batch", "variant", "S", "inner", "inner_kv", "hd", "hd_src", "Hkv", "type", "l2_touch",
+                      "split_off", "flags", "gate_act", "rowss_parts", "ldh", "H")
+GEMM_LAUNCH_PTRS = ("A", "W", "C", "bias", "heads_q", "heads_k", "heads_v", "rope_cos", "rope_sin", "rowss_in")
+GEMM_LAUNCH_FLAGS = {"bias": 1, "rowss_in": 2, "rope_cos": 8, "rope_sin": 16}
+
+
+def gemm_launch(launch, acc_scale: float = 1.0, out_scale: float = 1.0, rs_invd: float = 0.0, rs_eps: float = 0.0, **tensors) -> int:
+    """Test hook (vqs_debug_gemm_launch): ONE launch of the GEMM on caller tensors.  launch: dict of GEMM_LAUNCH_FIELDS (missing ones 0; the first 22 are
+    vqs_debug_gemm_plan's, whose flag bits are taken as given: the caller sets them, so that a test can also ask for a flag without its pointer); tensors: by
+    the names of GEMM_LAUNCH_PTRS.  Nothing is allocated, copied or checked here.  -> the hook's return code (0, or VQS_ERR_INVALID = -1 for a refusal)."""
+    unknown = (set(launch) - set(GEMM_LAUNCH_FIELDS)) | (set(tensors) - set(GEMM_LAUNCH_PTRS))
+    if unknown:
+        raise VqsError(f"gemm_launch: unknown fields {sorted(unknown)}")
+    ints = (ctypes.c_int32 * len(GEMM_LAUNCH_FIELDS))(*[int(launch.get(f, 0)) for f in GEMM_LAUNCH_FIELDS])
+    ptrs = (ctypes.c_void_p * len(GEMM_LAUNCH_PTRS))(*[_ptr(tensors.get(n)) for n in GEMM_LAUNCH_PTRS])
+    scales = (ctypes.c_float * 4)(acc_scale, out_scale, rs_invd, rs_eps)
+    return load_library().vqs_debug_gemm_launch(ctypes.cast(ints, ctypes.c_void_p), len(ints), ctypes.cast(ptrs, ctypes.c_void_p), len(ptrs),
+                                                ctypes.cast(scales, ctypes.c_void_p), 4, _stream_ptr())
 
 
 def gemm_resid_rms(A, W, hres, lnw, variant: int = 3):

@@ -56,6 +56,37 @@ int main() {
         assert(vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS - 1, g) == VQS_ERR_INVALID && vqs_debug_gemm_plan(nullptr, VQS_GEMM_PLAN_FIELDS, g) == VQS_ERR_INVALID &&
                vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS, nullptr) == VQS_ERR_INVALID);
     }
+    {   // the single-launch hook behind the same integers (+ H): everything it refuses, it refuses in host code, before any device call
+        int32_t l[VQS_GEMM_LAUNCH_FIELDS] = {136, 640, 128, 128, 128, 0, 6, 1, 10, 8, 384, 128, 128, 0, 1, 0}, g[5];
+        l[22] = 3;                                                                                                                            // gqa 3 : 1, 128-lane heads
+        int d = 0;
+        const void* ptrs[VQS_GEMM_LAUNCH_PTRS] = {&d, &d, nullptr, nullptr, &d, &d, &d, nullptr, nullptr, nullptr};
+        const float sc[VQS_GEMM_LAUNCH_SCALES] = {1.0f, 1.0f, 0.0f, 0.0f};
+        assert(vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS, g) == 1 && g[0] == 5 && g[3] == 3);                                                // the quad kernel, three tiles
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_PLAN_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        assert(vqs_debug_gemm_launch(nullptr, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, nullptr, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS - 1, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, nullptr, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES + 1, nullptr) == VQS_ERR_INVALID);
+        l[18] = 1;                                                                                                                            // bias flag without the vector
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        l[18] = 0; ptrs[7] = &d;                                                                                                              // a rope table without its flag
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        ptrs[7] = nullptr; l[22] = 0;                                                                                                         // no q heads
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        l[22] = 3; l[7] = 2;                                                                                                                  // batched launches, epilogue 7, split results: other hooks
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        l[7] = 1; l[17] = 4096;
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        l[17] = 0; l[6] = 7;
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        l[6] = 6; l[8] = 0;                                                                                                                   // the launcher's refusal: 128-lane heads under variant 0
+        assert(vqs_debug_gemm_plan(l, VQS_GEMM_PLAN_FIELDS, g) == 0);
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+        l[8] = 10; l[9] = 7;                                                                                                                  // S = 7 with 128-lane heads
+        assert(vqs_debug_gemm_launch(l, VQS_GEMM_LAUNCH_FIELDS, ptrs, VQS_GEMM_LAUNCH_PTRS, sc, VQS_GEMM_LAUNCH_SCALES, nullptr) == VQS_ERR_INVALID);
+    }
     assert(vqs_debug_gemm_batched(nullptr, nullptr, nullptr, 128, 608, 4096, 4096, 4096, 640, 3, 256, 0, 0, 0, 0, 0, 3, nullptr) == VQS_ERR_INVALID);
     {
         int dummy2 = 0;
