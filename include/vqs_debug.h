@@ -115,6 +115,13 @@ int vqs_debug_qwen_kv_assemble(const void* d_pk, const void* d_pv, const void* d
  *     *lds_bytes (may be NULL) = the launch's dynamic LDS bytes (0 when not launchable). */
 int vqs_debug_qwen_decode_attention(const void* d_q, const void* d_kc, const void* d_vc, const int32_t* d_len, void* d_out, int64_t out_plane, int32_t B,
                                     int32_t Hq, int32_t Hkv, int32_t Lmax, float scale, float vscale, int32_t mode, void* stream);
+/* vqs_debug_qwen_rows_attention: launch_qwen_rows_attn and nothing else -- the precise tail's attention over a row list (vqs_qwen_score_rows).
+ * q fp32 [Q, Hq * 128], k / v [R, Hkv, L, 128] (bf16, or IEEE fp16 with kv_f16 != 0: key scale folded into `scale`, output multiplied by vscale),
+ * row_sample / row_keys int32 [Q], out split-bf16 [Q, Hq * 128] with the lo plane out_plane (>= Q * Hq * 128) elements further.  Row r attends over
+ * sample row_sample[r] (outside [0, R): a zero row) with min(max(row_keys[r], 1), L) keys; the kernel form is vqs_debug_qwen_decode_attention_form's. */
+int vqs_debug_qwen_rows_attention(const void* d_q, const void* d_k, const void* d_v, const int32_t* d_row_sample, const int32_t* d_row_keys, void* d_out,
+                                  int64_t out_plane, int32_t Q, int32_t R, int32_t Hq, int32_t Hkv, int32_t L, float scale, int32_t kv_f16, float vscale,
+                                  void* stream);
 int vqs_debug_qwen_decode_rope_append(const void* d_qkv, const float* d_cos, const float* d_sin, const int32_t* d_len, void* d_q_out, void* d_kc, void* d_vc,
                                       int32_t B, int32_t Hq, int32_t Hkv, int32_t hd, int32_t half, int32_t Lmax, void* stream);
 int vqs_debug_qwen_decode_attention_form(int32_t Hq, int32_t Hkv, int32_t Lmax, int64_t* lds_bytes);

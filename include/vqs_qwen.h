@@ -170,6 +170,30 @@ int vqs_qwen_prefill_suffix(vqs_qwen_handle* h, const void* d_merged, const int3
                             int32_t Ls, const void* d_pkv, int32_t U, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv,
                             size_t kv_bytes, int32_t Lmax, void* stream);
 
+/* Logits of SEVERAL rows per sample in one pass: teacher-forced scoring of a multi-token answer (the prompt followed by the answer's
+ * first n - 1 tokens; the last n positions are the rows whose distributions the answer's tokens are read from).  vqs_qwen_score_rows is
+ * vqs_qwen_score, and vqs_qwen_score_suffix_rows is vqs_qwen_score_suffix, with a ROW LIST of Q entries in place of d_last_row:
+ *   d_row_index  int32 [Q]   the row of the pass's rows (B*L, or the B*Ls suffix rows) -- selects the embedding and the d_cos / d_sin row; in range
+ *   d_row_sample int32 [Q]   the sample whose K / V the row attends over, in [0, B); outside: the row's attention output is zero, nothing is read
+ *   d_row_keys   int32 [Q]   the keys it sees = its position in the WHOLE sequence + 1 (suffix: > Lp); clamped on the device to [1, L]
+ *   d_logits     fp32 [Q, t_vocab] out, in list order
+ * The identity list (row b = d_last_row[b], sample b, d_seq_len[b] keys) gives the logits of vqs_qwen_score / vqs_qwen_score_suffix bit for bit.
+ * Every listed row is evaluated by the precise tail (option "tail_precise", below): its own residual path with 16 significant bits, its attention
+ * in fp32 over the layer's K / V.  Those K / V -- the listed rows' own included -- come from the 16-bit prefill (bf16, or fp16 behind the
+ * layer's scale under option "fp16"), exactly as the last row's do in vqs_qwen_score.  Rows are independent of one another: a row's logits do
+ * not depend on which other rows are listed, nor on the order.
+ * Refused with VQS_ERR_INVALID before any launch: Q <= 0 or Q > the pass's rows, a NULL row array, option tail_precise = 0, t_vocab % 4 != 0, and
+ * every shape the extended entry point refuses; the *_bytes queries return 0 for such shapes. */
+size_t vqs_qwen_score_rows_workspace_bytes(const vqs_qwen_handle* h, int32_t B, int32_t L, int32_t Q);
+int vqs_qwen_score_rows(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_input_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                        const float* d_cos, const float* d_sin, int32_t B, int32_t L, const int32_t* d_row_index, const int32_t* d_row_sample,
+                        const int32_t* d_row_keys, int32_t Q, float* d_logits, void* d_ws, size_t ws_bytes, void* stream);
+size_t vqs_qwen_suffix_rows_workspace_bytes(const vqs_qwen_handle* h, int32_t B, int32_t Lp, int32_t Ls, int32_t Q);
+int vqs_qwen_score_suffix_rows(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                               const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int32_t B, int32_t Lp, int32_t Ls, const void* d_pkv,
+                               int32_t U, size_t pkv_bytes, const int32_t* d_row_index, const int32_t* d_row_sample, const int32_t* d_row_keys, int32_t Q,
+                               float* d_logits, void* d_ws, size_t ws_bytes, void* stream);
+
 /* Test hook (not part of the drop-in boundary): register a caller-owned device buffer for a named intermediate of the NEXT passes;
  * when a pass produces it, it is copied there on the pass's stream.  Names: vis.pre, vis.<i>.{h,xn0,q0,k0,q,k,v,attn,d_attn,xn1,ff,d_mlp},
  * vis.{h_out,xnm,mid,merged_w}; txt.emb, txt.<i>.{h,xn0,q0,k0,q,k,v,attn,d_attn,xn1,ff,d_mlp}, txt.{h_out,xnf}; of vqs_qwen_decode:

@@ -394,6 +394,311 @@ hipError_t launch_qwen_tail_attn(const float* q, const bf16_t* k, const bf16_t* 
     return launch_decode_attn_t<true>(q, k, v, count, out, B, Hq, Hkv, Lmax, scale, out_plane, s);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The precise tail over a ROW LIST (vqs_qwen_score_rows / vqs_qwen_score_suffix_rows, vqs_qwen.cpp): Q query rows, row r attending over the
+// K / V slabs of sample row_sample[r] with row_keys[r] keys (its absolute position + 1).  Several rows may share a sample (teacher-forced
+// answers) and the rows of one launch need not be in sample order.  The two kernels below are qwen_decode_attn_gqa_kernel<true, KVH> and
+// qwen_decode_attn_kernel<true, KVH> with the slab base and the key count taken from the row list and nothing else changed: fp32 q, the same
+// lane / wave partition of the key range, the same shuffle and wave-order reductions, unrounded fp32 probabilities, split-bf16 output --
+// so the identity list (row_sample[r] = r, row_keys = the lengths) gives launch_qwen_tail_attn's output bit for bit, and a row's output does
+// not depend on which other rows share its launch (tests/test_gpu_qwen_rows_kernels.py).  They are separate kernels rather than a further
+// template parameter of the two above so that the code objects of the existing kernels stay what the validated record holds.
+// Safety: row_sample[r] outside [0, R) writes a zero row (both planes) and reads nothing; row_keys[r] is clamped to [1, Lmax].
+// ---------------------------------------------------------------------------------------------------------------------------------
+template <bool KVH>
+__global__ void __launch_bounds__(256) qwen_rows_attn_head_kernel(const float* __restrict__ q_, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
+                                                                  const int* __restrict__ row_sample, const int* __restrict__ row_keys,
+                                                                  bf16_t* __restrict__ out, int R, int Hq, int Hkv, int Lmax, float scale,
+                                                                  long long out_plane, float vscale) {
+    constexpr int HD = 128;
+    extern __shared__ __attribute__((aligned(16))) float d_smem[];
+    __shared__ float qs[HD];
+    __shared__ float red[4];
+    __shared__ float part[4][HD];
+    const int h = blockIdx.x, r = blockIdx.y, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int hk = h / (Hq / Hkv);
+    const int b = row_sample[r];
+    if (b < 0 || b >= R) {      // block-uniform: no barrier has been reached
+        if (t < HD) {
+            out[((size_t)r * Hq + h) * HD + t] = 0;
+            out[out_plane + ((size_t)r * Hq + h) * HD + t] = 0;
+        }
+        return;
+    }
+    const int n = min(max(row_keys[r], 1), Lmax);
+    const bf16_t* K = kc + ((size_t)b * Hkv + hk) * Lmax * HD;
+    const bf16_t* V = vc + ((size_t)b * Hkv + hk) * Lmax * HD;
+    if (t < HD) qs[t] = q_[((size_t)r * Hq + h) * HD + t];
+    __syncthreads();
+    float mx = -3.0e38f;
+    for (int j = t; j < n; j += 256) {
+        const uint4* kr = reinterpret_cast<const uint4*>(K + (size_t)j * HD);
+        float acc = 0.0f;
+#pragma unroll
+        for (int c = 0; c < HD / 8; ++c) {
+            const uint4 u = kr[c];
+            const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float k0, k1;
+                d_cvt2(w4[e], KVH, k0, k1);
+                acc = fmaf(k0, qs[8 * c + 2 * e], acc);
+                acc = fmaf(k1, qs[8 * c + 2 * e + 1], acc);
+            }
+        }
+        const float tj = acc * scale;
+        d_smem[j] = tj;
+        mx = fmaxf(mx, tj);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    if (lane == 0) red[wv] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float ls = 0.0f;
+    for (int j = t; j < n; j += 256) {
+        const float p = __expf(d_smem[j] - mx);
+        d_smem[j] = p;
+        ls += p;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ls += __shfl_xor(ls, off);
+    if (lane == 0) red[wv] = ls;
+    __syncthreads();
+    const float l = (red[0] + red[1]) + (red[2] + red[3]);
+    float o0 = 0.0f, o1 = 0.0f;
+    for (int j = wv; j < n; j += 4) {
+        const uint32_t u = reinterpret_cast<const uint32_t*>(V + (size_t)j * HD)[lane];
+        const float p = d_smem[j];
+        float v0, v1;
+        d_cvt2(u, KVH, v0, v1);
+        o0 = fmaf(p, v0, o0);
+        o1 = fmaf(p, v1, o1);
+    }
+    part[wv][2 * lane] = o0;
+    part[wv][2 * lane + 1] = o1;
+    __syncthreads();
+    if (t < HD) {
+        float o = ((part[0][t] + part[1][t]) + (part[2][t] + part[3][t])) / l;
+        if (KVH) o *= vscale;
+        const bf16_t hi = d_f2bf(o);
+        out[((size_t)r * Hq + h) * HD + t] = hi;
+        out[out_plane + ((size_t)r * Hq + h) * HD + t] = d_f2bf(o - d_bf2f(hi));
+    }
+}
+
+template <bool KVH>
+__global__ void __launch_bounds__(64 * QD_NW) qwen_rows_attn_kernel(const float* __restrict__ q_, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
+                                                                    const int* __restrict__ row_sample, const int* __restrict__ row_keys,
+                                                                    bf16_t* __restrict__ out, int R, int Hq, int Hkv, int Lmax, float scale,
+                                                                    long long out_plane, float vscale) {
+    constexpr int HD = 128, U = 8;
+    extern __shared__ __attribute__((aligned(16))) float d_smem[];      // sc[G][Lp]
+    __shared__ float red[QD_NW][QD_GMAX];
+    __shared__ float stat[2][QD_GMAX];                                  // max, sum per head
+    __shared__ float part[QD_NW][QD_GMAX][HD];
+    const int hk = blockIdx.x, r = blockIdx.y, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int G = Hq / Hkv;
+    const int b = row_sample[r];
+    if (b < 0 || b >= R) {      // block-uniform: no barrier has been reached
+        for (int i = t; i < G * HD; i += 64 * QD_NW) {
+            out[((size_t)r * Hq + (size_t)hk * G) * HD + i] = 0;
+            out[out_plane + ((size_t)r * Hq + (size_t)hk * G) * HD + i] = 0;
+        }
+        return;
+    }
+    const int n = min(max(row_keys[r], 1), Lmax);
+    const int Lp = (Lmax + 3) & ~3;
+    float* sc = d_smem;
+    const bf16_t* K = kc + ((size_t)b * Hkv + hk) * Lmax * HD;
+    const bf16_t* V = vc + ((size_t)b * Hkv + hk) * Lmax * HD;
+    const int sub = lane >> 4, c = lane & 15;
+    auto cvt8 = [](const uint4& u, float (&f)[8]) {                     // a K / V chunk
+        const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d_cvt2(w4[e], KVH, f[2 * e], f[2 * e + 1]);
+    };
+    // ---- scores
+    {
+        float qf[QD_GMAX][8];
+#pragma unroll
+        for (int g = 0; g < QD_GMAX; ++g)
+            if (g < G) {
+                const size_t qo = ((size_t)r * Hq + (size_t)hk * G + g) * HD + 8 * c;
+                const float4 a = reinterpret_cast<const float4*>(q_ + qo)[0];
+                const float4 bq = reinterpret_cast<const float4*>(q_ + qo)[1];
+                qf[g][0] = a.x; qf[g][1] = a.y; qf[g][2] = a.z; qf[g][3] = a.w;
+                qf[g][4] = bq.x; qf[g][5] = bq.y; qf[g][6] = bq.z; qf[g][7] = bq.w;
+            }
+        float mx[QD_GMAX];
+#pragma unroll
+        for (int g = 0; g < QD_GMAX; ++g) mx[g] = -3.0e38f;
+        for (int j0 = wv * 4; j0 < n; j0 += 4 * QD_NW * U) {
+            uint4 kv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = j0 + 4 * QD_NW * u + sub;
+                kv[u] = j < n ? *reinterpret_cast<const uint4*>(K + (size_t)j * HD + 8 * c) : make_uint4(0u, 0u, 0u, 0u);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = j0 + 4 * QD_NW * u + sub;
+                float kf[8];
+                cvt8(kv[u], kf);
+#pragma unroll
+                for (int g = 0; g < QD_GMAX; ++g)
+                    if (g < G) {
+                        float d = 0.0f;
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) d = fmaf(qf[g][e], kf[e], d);
+                        d += __shfl_xor(d, 1);
+                        d += __shfl_xor(d, 2);
+                        d += __shfl_xor(d, 4);
+                        d += __shfl_xor(d, 8);
+                        const float tj = d * scale;
+                        if (j < n) {
+                            if (c == 0) sc[g * Lp + j] = tj;
+                            mx[g] = fmaxf(mx[g], tj);
+                        }
+                    }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < QD_GMAX; ++g)
+            if (g < G) {
+                float m = mx[g];
+                m = fmaxf(m, __shfl_xor(m, 16));
+                m = fmaxf(m, __shfl_xor(m, 32));
+                if (lane == 0) red[wv][g] = m;
+            }
+    }
+    __syncthreads();
+    if (t < G) {
+        float m = red[0][t];
+#pragma unroll
+        for (int i = 1; i < QD_NW; ++i) m = fmaxf(m, red[i][t]);
+        stat[0][t] = m;
+    }
+    __syncthreads();
+    // ---- probabilities (fp32, not rounded) and their sums
+    {
+        float ls[QD_GMAX];
+#pragma unroll
+        for (int g = 0; g < QD_GMAX; ++g) ls[g] = 0.0f;
+        for (int j = t; j < n; j += 64 * QD_NW)
+#pragma unroll
+            for (int g = 0; g < QD_GMAX; ++g)
+                if (g < G) {
+                    const float p = __expf(sc[g * Lp + j] - stat[0][g]);
+                    sc[g * Lp + j] = p;
+                    ls[g] += p;
+                }
+#pragma unroll
+        for (int g = 0; g < QD_GMAX; ++g)
+            if (g < G) {
+                float v = ls[g];
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+                if (lane == 0) red[wv][g] = v;
+            }
+    }
+    __syncthreads();
+    if (t < G) {
+        float v = red[0][t];
+#pragma unroll
+        for (int i = 1; i < QD_NW; ++i) v += red[i][t];
+        stat[1][t] = v;
+    }
+    // ---- output
+    {
+        float acc[QD_GMAX][8];
+#pragma unroll
+        for (int g = 0; g < QD_GMAX; ++g)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[g][e] = 0.0f;
+        for (int j0 = wv * 4; j0 < n; j0 += 4 * QD_NW * U) {
+            uint4 vv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = j0 + 4 * QD_NW * u + sub;
+                vv[u] = j < n ? *reinterpret_cast<const uint4*>(V + (size_t)j * HD + 8 * c) : make_uint4(0u, 0u, 0u, 0u);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = j0 + 4 * QD_NW * u + sub;
+                if (j < n) {
+                    float vf[8];
+                    cvt8(vv[u], vf);
+#pragma unroll
+                    for (int g = 0; g < QD_GMAX; ++g)
+                        if (g < G) {
+                            const float p = sc[g * Lp + j];
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) acc[g][e] = fmaf(p, vf[e], acc[g][e]);
+                        }
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < QD_GMAX; ++g)
+            if (g < G) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    float v = acc[g][e];
+                    v += __shfl_xor(v, 16);
+                    v += __shfl_xor(v, 32);
+                    if (sub == 0) part[wv][g][8 * c + e] = v;
+                }
+            }
+    }
+    __syncthreads();
+    for (int i = t; i < G * HD; i += 64 * QD_NW) {
+        const int g = i / HD, d = i - g * HD;
+        float o = part[0][g][d];
+#pragma unroll
+        for (int i2 = 1; i2 < QD_NW; ++i2) o += part[i2][g][d];
+        o = o / stat[1][g];
+        if (KVH) o *= vscale;
+        const bf16_t hi = d_f2bf(o);
+        out[((size_t)r * Hq + (size_t)hk * G + g) * HD + d] = hi;
+        out[out_plane + ((size_t)r * Hq + (size_t)hk * G + g) * HD + d] = d_f2bf(o - d_bf2f(hi));
+    }
+}
+
+template <bool KVH>
+static hipError_t launch_rows_attn_t(const float* q, const bf16_t* k, const bf16_t* v, const int* row_sample, const int* row_keys, bf16_t* out,
+                                     long long out_plane, int Q, int R, int Hq, int Hkv, int Lmax, float scale, float vscale, hipStream_t s) {
+    size_t lds = 0;
+    const int form = qwen_decode_attn_form(Hq, Hkv, Lmax, &lds);      // the decision launch_qwen_tail_attn takes for this geometry
+    if (form < 0) return hipErrorInvalidValue;
+    if (form == 1) {
+        if (lds > 48 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(qwen_rows_attn_kernel<KVH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((qwen_rows_attn_kernel<KVH>), dim3((unsigned)Hkv, (unsigned)Q), dim3(64 * QD_NW), lds, s, q, k, v, row_sample, row_keys, out, R, Hq, Hkv,
+                           Lmax, scale, out_plane, vscale);
+        return hipGetLastError();
+    }
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(qwen_rows_attn_head_kernel<KVH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((qwen_rows_attn_head_kernel<KVH>), dim3((unsigned)Hq, (unsigned)Q), dim3(256), lds, s, q, k, v, row_sample, row_keys, out, R, Hq, Hkv, Lmax,
+                       scale, out_plane, vscale);
+    return hipGetLastError();
+}
+
+// q fp32 [Q, Hq * 128] (rotated), k / v = the slabs of ALL R samples of the pass [R, Hkv, Lmax, 128] (bf16, or fp16 with kv_f16),
+// row_sample / row_keys int32 [Q]; out = split-bf16 [2][Q][Hq * 128], planes out_plane elements apart (out_plane >= Q * Hq * 128).
+hipError_t launch_qwen_rows_attn(const float* q, const bf16_t* k, const bf16_t* v, const int* row_sample, const int* row_keys, bf16_t* out,
+                                 long long out_plane, int Q, int R, int Hq, int Hkv, int Lmax, float scale, hipStream_t s, bool kv_f16, float vscale) {
+    if (Q <= 0 || Q > 65535 || R <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) != 0 || Lmax <= 0 || out_plane < (long long)Q * Hq * 128) return hipErrorInvalidValue;
+    if (kv_f16) return launch_rows_attn_t<true>(q, k, v, row_sample, row_keys, out, out_plane, Q, R, Hq, Hkv, Lmax, scale, vscale, s);
+    return launch_rows_attn_t<false>(q, k, v, row_sample, row_keys, out, out_plane, Q, R, Hq, Hkv, Lmax, scale, 1.0f, s);
+}
+
 // K / V of an fp16 prefill layer into the bf16 cache the decode step reads: dst[r][0 : cols) = bf16(fp16 src[r][0 : cols) * unscale),
 // rows `src_ld` / `dst_ld` elements apart (cols % 8 == 0)
 __global__ void __launch_bounds__(256) f16_to_bf16_rows_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int cols8, long long src_ld,

@@ -1403,6 +1403,13 @@ int vqs_debug_qwen_decode_attention(const void* q, const void* kc, const void* v
                                                     scale, (hipStream_t)stream, mode == 2, mode == 2 ? vscale : 1.0f));
 }
 
+int vqs_debug_qwen_rows_attention(const void* q, const void* k, const void* v, const int32_t* row_sample, const int32_t* row_keys, void* out, int64_t out_plane,
+                                  int32_t Q, int32_t R, int32_t Hq, int32_t Hkv, int32_t L, float scale, int32_t kv_f16, float vscale, void* stream) {
+    if (!q || !k || !v || !row_sample || !row_keys || !out) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_qwen_rows_attn((const float*)q, (const bf16_t*)k, (const bf16_t*)v, row_sample, row_keys, (bf16_t*)out, (long long)out_plane, Q, R,
+                                                    Hq, Hkv, L, scale, (hipStream_t)stream, kv_f16 != 0, kv_f16 ? vscale : 1.0f));
+}
+
 int vqs_debug_qwen_decode_rope_append(const void* qkv, const float* cs, const float* sn, const int32_t* len, void* q_out, void* kc, void* vc, int32_t B,
                                       int32_t Hq, int32_t Hkv, int32_t hd, int32_t half, int32_t Lmax, void* stream) {
     if (!qkv || !cs || !sn || !len || !q_out || !kc || !vc) return VQS_ERR_INVALID;

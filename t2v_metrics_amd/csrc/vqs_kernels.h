@@ -298,6 +298,11 @@ hipError_t launch_qwen_decode_attn(const bf16_t* q, const bf16_t* kc, const bf16
                                    int Hkv, int Lmax, float scale, hipStream_t s);
 hipError_t launch_qwen_tail_attn(const float* q, const bf16_t* k, const bf16_t* v, const int* count, bf16_t* out, long long out_plane, int B, int Hq,
                                  int Hkv, int Lmax, float scale, hipStream_t s, bool kv_f16 = false, float vscale = 1.0f);
+// launch_qwen_tail_attn over a row list: row r of Q attends over sample row_sample[r]'s slabs (of R) with row_keys[r] keys; the identity
+// list gives launch_qwen_tail_attn's bits (qwen_decode.hip)
+hipError_t launch_qwen_rows_attn(const float* q, const bf16_t* k, const bf16_t* v, const int* row_sample, const int* row_keys, bf16_t* out,
+                                 long long out_plane, int Q, int R, int Hq, int Hkv, int Lmax, float scale, hipStream_t s, bool kv_f16 = false,
+                                 float vscale = 1.0f);
 // Which kernel a launch_qwen_decode_attn / launch_qwen_tail_attn call takes (host arithmetic; the launcher and the test hook
 // vqs_debug_qwen_decode_attention_form share it): 1 = the grouped-query kernel (one block per key/value head, G = Hq / Hkv <= 8 rows of
 // ((Lmax + 3) & ~3) fp32 scores in dynamic LDS, up to 120 KiB), 0 = the per-query-head kernel (Lmax fp32 scores), -1 = not launchable.

@@ -430,15 +430,16 @@ static constexpr int TAIL_ROWS = 64;      // samples per chunk of the precise ta
 struct TxtWs {
     bf16_t *xn, *delta, *delta2, *q, *k, *v, *attn, *ff, *last;
     float* hidden;
-    // precise tail (vqs_qwen_handle::tail_precise): per-sample state for all B samples, chunk-sized operands
-    float *t_h, *t_delta;         // fp32 stream row and pending sub-layer output of every sample's last position [B, hidden]
+    // precise tail (vqs_qwen_handle::tail_precise): state of all its rows (one per sample, or the Q rows of a row list), chunk-sized operands
+    float *t_h, *t_delta;         // fp32 stream row and pending sub-layer output of every tail row [B or Q, hidden]
     float *t_qkv, *t_q;           // fp32 q|k|v row and rotated q of a chunk
     bf16_t *t_xn, *t_attn, *t_ff; // split-bf16 operands of a chunk: planes [2][rows][width]
     float* t_part;                // fp32 partials of a chunk's stacked launch
     size_t t_part_bytes;
     size_t total;
 };
-TxtWs carve_text(const vqs_qwen_handle* h, char* base, int B, int L) {
+// Q > 0: the tail runs over a row list of Q rows (vqs_qwen_score_rows); 0: one row per sample
+TxtWs carve_text(const vqs_qwen_handle* h, char* base, int B, int L, int Q = 0) {
     const vqs_qwen_config& c = h->c;
     Carver cv{base};
     TxtWs w{};
@@ -454,9 +455,9 @@ TxtWs carve_text(const vqs_qwen_handle* h, char* base, int B, int L) {
     w.ff = cv.take<bf16_t>(M * h->t_ffld);
     w.last = cv.take<bf16_t>((size_t)B * c.t_hidden);
     {   // precise tail: always laid out (a few hundred MB at 7B), so that the option can be toggled on a bound handle
-        const size_t Bc = (size_t)std::min(B, TAIL_ROWS), QN = (size_t)h->t_iq + 2 * h->t_ikv;
-        w.t_h = cv.take<float>((size_t)B * c.t_hidden);
-        w.t_delta = cv.take<float>((size_t)B * c.t_hidden);
+        const size_t Tn = (size_t)(Q > 0 ? Q : B), Bc = std::min(Tn, (size_t)TAIL_ROWS), QN = (size_t)h->t_iq + 2 * h->t_ikv;
+        w.t_h = cv.take<float>(Tn * c.t_hidden);
+        w.t_delta = cv.take<float>(Tn * c.t_hidden);
         w.t_qkv = cv.take<float>(Bc * QN);
         w.t_q = cv.take<float>(Bc * h->t_iq);
         w.t_xn = cv.take<bf16_t>(2 * Bc * c.t_hidden);
@@ -832,7 +833,8 @@ inline size_t kv_slab(const vqs_qwen_handle* h, int B, int Lmax) { return (size_
 // added afterwards), q|k|v, q after the rotary embedding, the softmax and the three sub-layer outputs stay fp32.  Its attention reads the
 // layer's K / V as the prefill left them (bf16, head-major, the row's own position included).  Same function as the prefill's last row
 // (HF Qwen2_5_VLDecoderLayer, modeling_qwen2_5_vl.py:720-787), evaluated closer to fp32 -- like the CLIP-FlanT5 row's precise decoder.
-// Cost: the language model's weights streamed once more per chunk of 64 samples (~1 % of the 7B pass at B = 64).
+// Cost: the language model's weights streamed once more per chunk of 64 rows (measured at 7B, B = 64: 17 ms = 2 % of the pass per chunk,
+// for the one chunk of the last rows and for every further chunk of a row list alike: profiles/qwen_teacher_forcing.jsonl).
 // ---------------------------------------------------------------------------------------------------------------------------------
 // One nn.Linear over K slices as batch entries (decode_slices: a function of the weight's shape only) into the fp32 partials
 // part[slices][rows][N]; *slices = their number.  The caller's reducer adds the slices and applies the epilogue.
@@ -857,12 +859,23 @@ int tail_linear(vqs_qwen_handle* h, const bf16_t* A2, int lda, const bf16_t* W, 
     return VQS_OK;
 }
 
-// One decoder layer of the tail for every chunk of <= TAIL_ROWS samples; w.k / w.v hold THIS layer's K (rotated) and V of the prefill.
-int tail_layer(vqs_qwen_handle* h, const TxtWs& w, int i, const bf16_t* ln1, const bf16_t* ln2, const int32_t* d_seq_len, const int32_t* d_last_row,
-               const float* d_cos, const float* d_sin, int B, int L, bool first, hipStream_t st, bool kv_f16 = false, float kv_sigma = 1.0f) {
+// The rows the tail evaluates.  Default: every sample's last position (row d_last_row[b], d_seq_len[b] keys of sample b).  With a row list
+// (vqs_qwen_score_rows / vqs_qwen_score_suffix_rows): n rows, row r = row index[r] of the pass's R * S rows (embedding and cos / sin row),
+// attending over sample sample[r]'s slabs with keys[r] keys.  Every tail step but the attention is row-independent, so the list is fed
+// through in chunks of TAIL_ROWS wherever they fall; a chunk may split a sample's rows, and its attention gets the slabs of the whole pass.
+struct TailRows {
+    const int32_t *index = nullptr, *sample = nullptr, *keys = nullptr;
+    int n = 0;
+    bool listed() const { return sample != nullptr; }
+};
+
+// One decoder layer of the tail for every chunk of <= TAIL_ROWS rows; w.k / w.v hold THIS layer's K (rotated) and V of the prefill.
+int tail_layer(vqs_qwen_handle* h, const TxtWs& w, int i, const bf16_t* ln1, const bf16_t* ln2, const TailRows& tr,
+               const float* d_cos, const float* d_sin, int R, int L, bool first, hipStream_t st, bool kv_f16 = false, float kv_sigma = 1.0f) {
     const vqs_qwen_config& c = h->c;
     const int TH = c.t_hidden, IQ = h->t_iq, IKV = h->t_ikv, QN = IQ + 2 * IKV;
     const float scale = 1.0f / sqrtf((float)h->t_hd);
+    const int B = tr.n;
     for (int c0 = 0; c0 < B; c0 += TAIL_ROWS) {
         const int rows = std::min(TAIL_ROWS, B - c0);
         float* th = w.t_h + (size_t)c0 * TH;
@@ -870,10 +883,14 @@ int tail_layer(vqs_qwen_handle* h, const TxtWs& w, int i, const bf16_t* ln1, con
         // ---- attention sub-layer
         VQS_HIP(h, vqs::launch_rmsnorm_split(th, first ? nullptr : td, ln1, w.t_xn, (long long)rows * TH, rows, TH, c.t_eps, st), "tail input_layernorm");
         VQS_RUN(tail_linear(h, w.t_xn, TH, h->t_qkv_w[i], TH, h->t_qkv_b[i], rows, QN, TH, vqs::SUM_F32, w.t_qkv, QN, 0, w, st, "tail qkv"));
-        VQS_HIP(h, vqs::launch_qwen_tail_rope_q(w.t_qkv, QN, d_cos, d_sin, d_last_row + c0, w.t_q, rows, c.t_heads, HDP, h->t_hd / 2, st), "tail rope");
+        VQS_HIP(h, vqs::launch_qwen_tail_rope_q(w.t_qkv, QN, d_cos, d_sin, tr.index + c0, w.t_q, rows, c.t_heads, HDP, h->t_hd / 2, st), "tail rope");
         // kv_f16: the layer's K / V are the fp16 prefill's tensors behind kv_sigma (the tail's own q is in true units)
-        VQS_HIP(h, vqs::launch_qwen_tail_attn(w.t_q, w.k + (size_t)c0 * L * IKV, w.v + (size_t)c0 * L * IKV, d_seq_len + c0, w.t_attn, (long long)rows * IQ, rows,
-                                           c.t_heads, c.t_kv_heads, L, scale / kv_sigma, st, kv_f16, 1.0f / kv_sigma), "tail attention");
+        if (tr.listed())
+            VQS_HIP(h, vqs::launch_qwen_rows_attn(w.t_q, w.k, w.v, tr.sample + c0, tr.keys + c0, w.t_attn, (long long)rows * IQ, rows, R, c.t_heads, c.t_kv_heads, L,
+                                               scale / kv_sigma, st, kv_f16, 1.0f / kv_sigma), "tail attention (row list)");
+        else
+            VQS_HIP(h, vqs::launch_qwen_tail_attn(w.t_q, w.k + (size_t)c0 * L * IKV, w.v + (size_t)c0 * L * IKV, tr.keys + c0, w.t_attn, (long long)rows * IQ, rows,
+                                               c.t_heads, c.t_kv_heads, L, scale / kv_sigma, st, kv_f16, 1.0f / kv_sigma), "tail attention");
         VQS_RUN(tail_linear(h, w.t_attn, IQ, h->t_o_w[i], IQ, nullptr, rows, TH, IQ, vqs::SUM_F32, td, TH, 0, w, st, "tail o_proj"));
         // ---- gated FFN
         VQS_HIP(h, vqs::launch_rmsnorm_split(th, td, ln2, w.t_xn, (long long)rows * TH, rows, TH, c.t_eps, st), "tail post_attention_layernorm");
@@ -885,7 +902,7 @@ int tail_layer(vqs_qwen_handle* h, const TxtWs& w, int i, const bf16_t* ln1, con
     return VQS_OK;
 }
 
-// final norm + lm_head of the tail -> d_logits [B, vocab] fp32
+// final norm + lm_head of the tail -> d_logits [B, vocab] fp32 (B = the tail's rows)
 int tail_head(vqs_qwen_handle* h, const TxtWs& w, const bf16_t* fin, const bf16_t* head, float* d_logits, int B, hipStream_t st) {
     const vqs_qwen_config& c = h->c;
     const int TH = c.t_hidden;
@@ -917,9 +934,9 @@ struct SharedWs {
     int* key_len = nullptr;                // prefix pass: Lp per prefix
     size_t total = 0;
 };
-SharedWs carve_shared(const vqs_qwen_handle* h, char* base, int R, int Lp, int Ls, bool suffix) {
+SharedWs carve_shared(const vqs_qwen_handle* h, char* base, int R, int Lp, int Ls, bool suffix, int Q = 0) {
     SharedWs s;
-    s.w = carve_text(h, base, R, suffix ? Lp + Ls : Lp);
+    s.w = carve_text(h, base, R, suffix ? Lp + Ls : Lp, Q);
     Carver cv{base};
     cv.off = s.w.total;
     if (suffix) {
@@ -953,11 +970,15 @@ struct TextPass {
     int Lmax = 0;
     const int32_t *d_seq_len = nullptr, *d_last_row = nullptr;
     float* d_logits = nullptr;
+    // optional row list (FULL and SUFFIX; needs the precise tail): Q > 0 replaces "the last row of every sample" as the rows the tail
+    // evaluates, d_logits is [Q, vocab] and d_last_row is not read
+    const int32_t *d_row_index = nullptr, *d_row_sample = nullptr, *d_row_keys = nullptr;
+    int Q = 0;
 };
 SharedWs carve_pass(const vqs_qwen_handle* h, char* base, const TextPass& t) {
-    if (t.mode != TextPass::FULL) return carve_shared(h, base, t.R, t.Lp, t.Ls, t.mode == TextPass::SUFFIX);
+    if (t.mode != TextPass::FULL) return carve_shared(h, base, t.R, t.Lp, t.Ls, t.mode == TextPass::SUFFIX, t.Q);
     SharedWs s;
-    s.w = carve_text(h, base, t.R, t.L);
+    s.w = carve_text(h, base, t.R, t.L, t.Q);
     s.total = s.w.total;
     return s;
 }
@@ -994,6 +1015,10 @@ int text_pass(vqs_qwen_handle* h, const TextPass& t, const void* d_merged, const
     const vqs_qwen_handle::LayerSites one{};
     const bool rope_in_gemm = F && h->rope_fused != 0 && h->t_hd == HDP;      // K12: 128-lane heads, scaled fp16 family (gemm_quad.inc ROPE)
     const bool tail = !prefix && h->tail_precise != 0 && (c.t_vocab % 4) == 0 && (c.t_hidden % 4) == 0;
+    TailRows tr;      // the entry points refuse a row list without the tail
+    if (t.Q > 0) { tr.index = t.d_row_index; tr.sample = t.d_row_sample; tr.keys = t.d_row_keys; tr.n = t.Q; }
+    else { tr.index = t.d_last_row; tr.keys = t.d_seq_len; tr.n = R; }
+    if (t.Q > 0 && !tail) return fail(h, VQS_ERR_INVALID, "row list: needs the precise tail");
 
     // ---- the steps in which the modes differ
     struct KV { bf16_t *k, *v; };
@@ -1036,7 +1061,7 @@ int text_pass(vqs_qwen_handle* h, const TextPass& t, const void* d_merged, const
     VQS_HIP(h, hipMemsetAsync(w.ff, 0, (size_t)M * h->t_ffld * sizeof(bf16_t), st), "clear ff padding");
     VQS_TAP("txt", -1, "emb", w.hidden, (size_t)M * TH);
     if (tail)      // the tail's starting state: the embedding rows of the last positions (fp32 copies of bf16 values: exact)
-        VQS_HIP(h, vqs::launch_gather_rows_f32(w.hidden, t.d_last_row, w.t_h, R, TH, TH, st), "tail embed rows");
+        VQS_HIP(h, vqs::launch_gather_rows_f32(w.hidden, tr.index, w.t_h, tr.n, TH, TH, st), "tail embed rows");
     if (prefix) VQS_HIP(h, hipMemsetD32Async((hipDeviceptr_t)ws.key_len, t.Lp, (size_t)R, st), "prefix key lengths");
 
     const bf16_t* pend = nullptr;
@@ -1076,7 +1101,7 @@ int text_pass(vqs_qwen_handle* h, const TextPass& t, const void* d_merged, const
         VQS_RUN(attention(att, scale / (sc.qkv.sigma * sc.qkv.sigma)));
         VQS_TAP("txt", i, "attn", w.attn, (size_t)M * IQ);
         if (tail)      // this layer's K / V are in w.k / w.v until the next layer's qkv launch (SUFFIX: assemble)
-            VQS_RUN(tail_layer(h, w, i, ln1, ln2, t.d_seq_len, t.d_last_row, d_cos, d_sin, R, L, i == 0, st, F, sc.qkv.sigma));
+            VQS_RUN(tail_layer(h, w, i, ln1, ln2, tr, d_cos, d_sin, R, L, i == 0, st, F, sc.qkv.sigma));
         {
             GemmCall g{w.attn, F ? h->t_o_h[i] : h->t_o_w[i], w.delta};
             g.M = M; g.N = TH; g.K = IQ; g.lda = IQ; g.ldw = IQ; g.ldc = TH; g.epi = vqs::EPI_BF16;
@@ -1110,7 +1135,7 @@ int text_pass(vqs_qwen_handle* h, const TextPass& t, const void* d_merged, const
     VQS_RUN(norm(pend_attn ? pend_attn : pend, fin, pend_attn ? pend : nullptr, true, pend_attn ? s_pend_attn : s_pend, s_pend, 1.0f, true, "final norm"));
     VQS_TAP("txt", -1, "h_out", w.hidden, (size_t)M * TH);
     VQS_RUN(tap2d(h, "txt", -1, "xnf", w.xn, TH, M, XLD, st));
-    if (tail) return tail_head(h, w, fin, head, t.d_logits, R, st);
+    if (tail) return tail_head(h, w, fin, head, t.d_logits, tr.n, st);
     VQS_HIP(h, vqs::launch_gather_rows_bf16(w.xn, nullptr, t.d_last_row, w.last, R, TH, XLD, TH, st), "last positions");
     {
         GemmCall g{w.last, head, t.d_logits};
@@ -1120,22 +1145,36 @@ int text_pass(vqs_qwen_handle* h, const TextPass& t, const void* d_merged, const
     return VQS_OK;
 }
 
-// vqs_qwen_score / vqs_qwen_prefill (cached: the pass also fills the decode cache)
+// A row list is refused BEFORE anything else of its call is looked at (and so before any launch): sizes, then the arrays, then the options
+// it needs -- the precise tail, whose lm_head reduction takes vocabularies that are multiples of 4.  m_rows = the pass's rows (0: its
+// shape is invalid).
+int check_row_list(vqs_qwen_handle* h, const TailRows& r, int64_t m_rows, const char* who) {
+    if (m_rows <= 0 || r.n <= 0 || r.n > m_rows)
+        return fail(h, VQS_ERR_INVALID, std::string(who) + ": need a valid pass shape and 0 < Q <= its rows");
+    if (!r.index || !r.sample || !r.keys) return fail(h, VQS_ERR_INVALID, std::string(who) + ": null row array");
+    if (!h->tail_precise) return fail(h, VQS_ERR_INVALID, std::string(who) + ": a row list is evaluated by the precise tail; option tail_precise is 0");
+    if (h->c.t_vocab % 4) return fail(h, VQS_ERR_INVALID, std::string(who) + ": the precise tail needs t_vocab % 4 == 0");
+    return VQS_OK;
+}
+
+// vqs_qwen_score / vqs_qwen_prefill (cached: the pass also fills the decode cache) / vqs_qwen_score_rows (rows)
 int full_entry(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
                const int32_t* d_last_row, const float* d_cos, const float* d_sin, int32_t B, int32_t L, float* d_logits, void* d_ws, size_t ws_bytes,
-               void* d_kv, size_t kv_bytes, int32_t Lmax, bool cached, void* stream) {
+               void* d_kv, size_t kv_bytes, int32_t Lmax, bool cached, void* stream, const TailRows* rows = nullptr) {
     if (!h) return VQS_ERR_INVALID;
+    if (rows) VQS_RUN(check_row_list(h, *rows, B > 0 && L > 0 ? (int64_t)B * L : 0, "score_rows"));
     if (cached) {
         if (!d_kv || Lmax < L || kv_bytes < vqs_qwen_kv_bytes(h, B, Lmax)) return fail(h, VQS_ERR_WORKSPACE, "prefill: KV cache missing or too small");
         if (Lmax > VQS_QWEN_MAX_CACHE_POSITIONS)      // the decode step's one-row attention keeps Lmax fp32 scores in LDS: refuse BEFORE the prefill is spent
             return fail(h, VQS_ERR_INVALID, "prefill: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
     }
     if (!h->bound) return fail(h, VQS_ERR_STATE, "score: weights not bound");
-    if (!d_merged || !d_ids || !d_vis_slot || !d_seq_len || !d_last_row || !d_cos || !d_sin || !d_logits || !d_ws)
+    if (!d_merged || !d_ids || !d_vis_slot || !d_seq_len || (!d_last_row && !rows) || !d_cos || !d_sin || !d_logits || !d_ws)
         return fail(h, VQS_ERR_INVALID, "score: null argument");
     if (B <= 0 || L <= 0) return fail(h, VQS_ERR_INVALID, "score: need B > 0, L > 0");
     TextPass t{TextPass::FULL, B, L, L};
     t.d_kv = cached ? d_kv : nullptr; t.Lmax = Lmax; t.d_seq_len = d_seq_len; t.d_last_row = d_last_row; t.d_logits = d_logits;
+    if (rows) { t.d_row_index = rows->index; t.d_row_sample = rows->sample; t.d_row_keys = rows->keys; t.Q = rows->n; }
     if (ws_bytes < carve_pass(h, nullptr, t).total) return fail(h, VQS_ERR_WORKSPACE, "score: workspace too small");
     if (h->fp16_active && L < 8) return fail(h, VQS_ERR_INVALID, "score: the fp16 forms need L >= 8 (option fp16 = 0 runs any)");
     return text_pass(h, t, d_merged, d_ids, d_vis_slot, d_cos, d_sin, d_ws, (hipStream_t)stream);
@@ -1144,15 +1183,16 @@ int full_entry(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, c
 int suffix_entry(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
                  const int32_t* d_last_row, const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int32_t B, int32_t Lp, int32_t Ls,
                  const void* d_pkv, int32_t U, size_t pkv_bytes, float* d_logits, void* d_ws, size_t ws_bytes, void* d_kv, size_t kv_bytes,
-                 int32_t Lmax, bool cached, void* stream) {
+                 int32_t Lmax, bool cached, void* stream, const TailRows* rows = nullptr) {
     if (!h) return VQS_ERR_INVALID;
     // sizes first: an invalid shape is refused whatever else is wrong with the call
+    if (rows) VQS_RUN(check_row_list(h, *rows, suffix_shape_ok(B, Lp, Ls) && prefix_shape_ok(U, Lp) ? (int64_t)B * Ls : 0, "score_suffix_rows"));
     if (!suffix_shape_ok(B, Lp, Ls) || !prefix_shape_ok(U, Lp))
         return fail(h, VQS_ERR_INVALID, "score_suffix: need B, U > 0, Lp a multiple of 32 (>= 32), Ls >= 8, Lp + Ls <= " + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS));
     if (cached && Lmax > VQS_QWEN_MAX_CACHE_POSITIONS)
         return fail(h, VQS_ERR_INVALID, "prefill_suffix: Lmax exceeds the decode kernel's limit (" + std::to_string(VQS_QWEN_MAX_CACHE_POSITIONS) + " cache positions)");
     if (!h->bound) return fail(h, VQS_ERR_STATE, "score_suffix: weights not bound");
-    if (!d_merged || !d_ids || !d_vis_slot || !d_seq_len || !d_last_row || !d_cos || !d_sin || !d_media_idx || !d_pkv || !d_logits || !d_ws)
+    if (!d_merged || !d_ids || !d_vis_slot || !d_seq_len || (!d_last_row && !rows) || !d_cos || !d_sin || !d_media_idx || !d_pkv || !d_logits || !d_ws)
         return fail(h, VQS_ERR_INVALID, "score_suffix: null argument");
     if (pkv_bytes < vqs_qwen_prefix_kv_bytes(h, U, Lp)) return fail(h, VQS_ERR_WORKSPACE, "score_suffix: prefix store too small");
     if (cached) {
@@ -1162,6 +1202,7 @@ int suffix_entry(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids,
     TextPass t{TextPass::SUFFIX, B, Ls, Lp + Ls};
     t.U = U; t.Lp = Lp; t.Ls = Ls; t.d_media_idx = d_media_idx; t.d_pkv = d_pkv; t.d_kv = cached ? d_kv : nullptr; t.Lmax = Lmax;
     t.d_seq_len = d_seq_len; t.d_last_row = d_last_row; t.d_logits = d_logits;
+    if (rows) { t.d_row_index = rows->index; t.d_row_sample = rows->sample; t.d_row_keys = rows->keys; t.Q = rows->n; }
     if (ws_bytes < carve_pass(h, nullptr, t).total) return fail(h, VQS_ERR_WORKSPACE, "shared prefix: workspace too small");
     return text_pass(h, t, d_merged, d_ids, d_vis_slot, d_cos, d_sin, d_ws, (hipStream_t)stream);
 }
@@ -1217,6 +1258,19 @@ int vqs_qwen_score(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_in
                    int32_t L, float* d_logits, void* d_ws, size_t ws_bytes, void* stream) {
     return full_entry(h, d_merged, d_input_ids, d_vis_slot, d_seq_len, d_last_row, d_cos, d_sin, B, L, d_logits, d_ws, ws_bytes, nullptr, 0, 0, false,
                       stream);
+}
+
+size_t vqs_qwen_score_rows_workspace_bytes(const vqs_qwen_handle* h, int32_t B, int32_t L, int32_t Q) {
+    if (!h || B <= 0 || L <= 0 || Q <= 0 || Q > (int64_t)B * L) return 0;
+    return carve_text(h, nullptr, B, L, Q).total;
+}
+
+int vqs_qwen_score_rows(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_input_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                        const float* d_cos, const float* d_sin, int32_t B, int32_t L, const int32_t* d_row_index, const int32_t* d_row_sample,
+                        const int32_t* d_row_keys, int32_t Q, float* d_logits, void* d_ws, size_t ws_bytes, void* stream) {
+    TailRows r;
+    r.index = d_row_index; r.sample = d_row_sample; r.keys = d_row_keys; r.n = Q;
+    return full_entry(h, d_merged, d_input_ids, d_vis_slot, d_seq_len, nullptr, d_cos, d_sin, B, L, d_logits, d_ws, ws_bytes, nullptr, 0, 0, false, stream, &r);
 }
 
 size_t vqs_qwen_kv_bytes(const vqs_qwen_handle* h, int32_t B, int32_t Lmax) {
@@ -1311,6 +1365,21 @@ size_t vqs_qwen_prefix_workspace_bytes(const vqs_qwen_handle* h, int32_t U, int3
 size_t vqs_qwen_suffix_workspace_bytes(const vqs_qwen_handle* h, int32_t B, int32_t Lp, int32_t Ls) {
     if (!h || !suffix_shape_ok(B, Lp, Ls)) return 0;
     return carve_shared(h, nullptr, B, Lp, Ls, true).total;
+}
+
+size_t vqs_qwen_suffix_rows_workspace_bytes(const vqs_qwen_handle* h, int32_t B, int32_t Lp, int32_t Ls, int32_t Q) {
+    if (!h || !suffix_shape_ok(B, Lp, Ls) || Q <= 0 || Q > (int64_t)B * Ls) return 0;
+    return carve_shared(h, nullptr, B, Lp, Ls, true, Q).total;
+}
+
+int vqs_qwen_score_suffix_rows(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const int32_t* d_seq_len,
+                               const float* d_cos, const float* d_sin, const int32_t* d_media_idx, int32_t B, int32_t Lp, int32_t Ls, const void* d_pkv,
+                               int32_t U, size_t pkv_bytes, const int32_t* d_row_index, const int32_t* d_row_sample, const int32_t* d_row_keys, int32_t Q,
+                               float* d_logits, void* d_ws, size_t ws_bytes, void* stream) {
+    TailRows r;
+    r.index = d_row_index; r.sample = d_row_sample; r.keys = d_row_keys; r.n = Q;
+    return suffix_entry(h, d_merged, d_ids, d_vis_slot, d_seq_len, nullptr, d_cos, d_sin, d_media_idx, B, Lp, Ls, d_pkv, U, pkv_bytes, d_logits, d_ws, ws_bytes,
+                        nullptr, 0, 0, false, stream, &r);
 }
 
 int vqs_qwen_prefix(vqs_qwen_handle* h, const void* d_merged, const int32_t* d_ids, const int32_t* d_vis_slot, const float* d_cos, const float* d_sin,

@@ -89,6 +89,7 @@ _SIGNATURES = {
     "vqs_debug_qwen_decode_attention": (_c_i32, [_c_vp] * 5 + [_c_i64] + [_c_i32] * 4 + [ctypes.c_float, ctypes.c_float, _c_i32, _c_vp]),
     "vqs_debug_qwen_decode_rope_append": (_c_i32, [_c_vp] * 7 + [_c_i32] * 6 + [_c_vp]),
     "vqs_debug_qwen_decode_attention_form": (_c_i32, [_c_i32] * 3 + [ctypes.POINTER(_c_i64)]),
+    "vqs_debug_qwen_rows_attention": (_c_i32, [_c_vp] * 6 + [_c_i64] + [_c_i32] * 5 + [ctypes.c_float, _c_i32, ctypes.c_float, _c_vp]),
     "vqs_debug_rmsnorm_split": (_c_i32, [_c_vp] * 4 + [_c_i64, _c_i32, _c_i32, ctypes.c_float, _c_vp]),
     "vqs_debug_sum_planes": (_c_i32, [_c_vp, _c_i32, _c_i64] + [_c_i32] * 4 + [_c_vp, _c_i32, _c_i64, _c_vp, _c_i32, _c_vp]),
     "vqs_debug_reduce_slices": (_c_i32, [_c_vp, _c_i32, _c_i64, _c_vp, _c_vp]),

@@ -396,7 +396,12 @@ class Qwen25VLModel(VQAScoreModel):
 
     @torch.no_grad()
     def forward(self, images: List[str], texts: List[str], fps=None, question_template: str = default_question_template,
-                answer_template: str = default_answer_template, max_new_tokens: int = 1, temperature: float = 1.0) -> torch.Tensor:
+                answer_template: str = default_answer_template, max_new_tokens: int = 1, temperature: float = 1.0,
+                teacher_forcing: bool = False) -> torch.Tensor:
+        """teacher_forcing=True: forward_teacher_forcing (the answer's tokens are forced, not generated); False: the reference's rollout."""
+        if teacher_forcing:
+            return self.forward_teacher_forcing(images, texts, fps=fps, question_template=question_template, answer_template=answer_template,
+                                                max_new_tokens=max_new_tokens, temperature=temperature)
         scores = torch.zeros(len(images), dtype=torch.float32)
         specials = self._special_ids()
         # ---- score the answer tokens from the LAST positions of the generated scores (:239-289)
@@ -476,6 +481,106 @@ class Qwen25VLModel(VQAScoreModel):
             probs.append(prob)
             traces.append(trace)
         return torch.tensor(probs), traces
+
+    # ------------------------------------------------------------------ teacher-forced scoring
+    def _teacher_scores(self, *args):
+        return self._with_bf16_fallback(lambda: self._teacher_scores_impl(*args))
+
+    def _teacher_scores_impl(self, images, texts, fps, question_template, answer_template, max_new_tokens):
+        """Front half of the teacher-forced methods; _generate_scores_impl's batching (one tower pass per distinct medium, windows of
+        max_batch, the shared prefix with share_prefix) with ONE language-model pass per window and no generation: sample i's sequence is
+        its prompt followed by the first n - 1 answer tokens, n = min(len(answer), max_new_tokens), and its last n positions are scored
+        (QwenEngine.score_rows).  -> per sample (processed score rows [n, vocab], the n forced answer ids)."""
+        assert len(images) == len(texts), "Number of images/videos and texts must match"
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        if not hasattr(self.engine, "score_rows"):
+            raise NotImplementedError(f"teacher forcing needs an engine with score_rows(merged, input_ids, attention_mask, grids, n_rows) "
+                                      f"(QwenEngine has it); {type(self.engine).__name__} does not")
+        questions = [question_template.format(t) for t in texts]
+        answers = [answer_template.format(t) for t in texts]
+        prepared, kinds, media_of = self._prepare_media(images, fps)
+        out = [None] * len(images)
+        share = getattr(self, "share_prefix", False) and hasattr(self.engine, "score_rows_shared")
+        for g, idxs, merged_of in self._media_windows(prepared, media_of):
+            for s in range(0, len(idxs), self.max_batch):
+                chunk = idxs[s: s + self.max_batch]
+                merged = torch.cat([merged_of[media_of[i]] for i in chunk])
+                n_tok = g[0] * g[1] * g[2] // self.cfg.vision.merge_unit
+                prompts = [self.build_ids(questions[i], kinds[media_of[i]], n_tok) for i in chunk]
+                a_ids = [list(self.tokenizer.encode(answers[i], add_special_tokens=False)) for i in chunk]
+                if any(len(a) < 1 for a in a_ids):
+                    raise ValueError("empty answer")
+                a_ids = [a[:max_new_tokens] for a in a_ids]      # the reference scores what was generated; here: what was asked for
+                n_rows = [len(a) for a in a_ids]
+                rows = [pr + a[:-1] for pr, a in zip(prompts, a_ids)]
+                L = max(len(r) for r in rows)
+                ids = torch.zeros(len(rows), L, dtype=torch.long)
+                mask = torch.zeros(len(rows), L, dtype=torch.long)
+                for k, r in enumerate(rows):
+                    ids[k, : len(r)] = torch.tensor(r)
+                    mask[k, : len(r)] = 1
+                grids = [g] * len(chunk)
+                logits = self.engine.score_rows_shared(merged, ids, mask, grids, [media_of[i] for i in chunk], n_rows) if share else None
+                if logits is None:
+                    logits = self.engine.score_rows(merged, ids, mask, grids, n_rows)
+                if getattr(self.engine, "fp16_active", False) and not bool(torch.isfinite(logits).all()):
+                    raise _NonFiniteUnderFp16()
+                q0 = 0
+                for k, i in enumerate(chunk):
+                    # row t is HF's generation step t: the repetition penalty sees the prompt and the t answer tokens before it
+                    proc = self._processed_scores(logits[q0: q0 + n_rows[k]], [prompts[k] + a_ids[k][:t] for t in range(n_rows[k])])
+                    out[i] = (proc, a_ids[k])
+                    q0 += n_rows[k]
+        return out
+
+    @torch.no_grad()
+    def forward_with_trace_teacher_forcing(self, images: List[str], texts: List[str], fps=None, question_template: str = default_question_template,
+                                           answer_template: str = default_answer_template, max_new_tokens: int = 1, temperature: float = 1.0,
+                                           debug: bool = False) -> Tuple[torch.Tensor, List[Dict]]:
+        """P(answer | medium, question) with the answer's tokens FORCED: a = encode(answer), n = min(len(a), max_new_tokens), one pass
+        over prompt + a[:n-1]; p_t = softmax(processed row t / temperature)[a[t]] with row t the distribution after prompt + a[:t] (processed as
+        HF's generation step t: repetition penalty over prompt + a[:t]); score = (prod p_t)^(1/n).  Where the greedy rollout of
+        forward_with_trace(max_new_tokens=n) produces exactly a[:n] the two methods read the same distributions; where it does not, the
+        rollout reads token t from a distribution conditioned on other tokens, and only this method is P(answer).  Nothing is generated,
+        so there is no trailing-special-token rule.  The trace has forward_with_trace's keys (score_position 'teacher_forcing', the forced
+        tokens as generated / scored text); each token detail also carries 'greedy_token_id' and 'is_greedy': whether a rollout that had
+        followed the answer so far would have produced this token."""
+        tok = self.tokenizer
+        probs, traces = [], []
+        for idx, (rows, a_ids) in enumerate(self._teacher_scores(images, texts, fps, question_template, answer_template, max_new_tokens)):
+            n = len(a_ids)
+            p = self._token_probs(rows, torch.tensor(a_ids), temperature)
+            dist = torch.softmax(rows.float() / temperature, dim=-1)
+            top_p, top_i = torch.topk(dist, 5, dim=-1)
+            greedy = rows.argmax(-1).cpu().tolist()
+            details = []
+            for t in range(n):
+                details.append({'position': t, 'expected_token_id': a_ids[t], 'expected_token_text': tok.decode([a_ids[t]]),
+                                'probability': float(p[t]),
+                                'top_alternatives': [{'token_id': int(ti), 'token_text': tok.decode([int(ti)]), 'probability': float(tp)}
+                                                     for tp, ti in zip(top_p[t].tolist(), top_i[t].tolist())],
+                                'greedy_token_id': int(greedy[t]), 'is_greedy': int(greedy[t]) == int(a_ids[t])})
+            prob = float(torch.prod(p.double()) ** (1.0 / n))
+            text = tok.decode(a_ids, skip_special_tokens=True)
+            trace = {'generated_text': text, 'generated_length': n, 'score_position': 'teacher_forcing', 'score_start_idx': 0,
+                     'scored_indices': list(range(n)), 'scored_tokens_text': text, 'probability': prob, 'token_details': details}
+            if debug:
+                print(f"Sample {idx + 1}/{len(images)}: {images[idx]} | {texts[idx]}\n  forced: {text!r}; greedy at every step: "
+                      f"{all(d['is_greedy'] for d in details)}; probability {prob:.6f}")
+            probs.append(prob)
+            traces.append(trace)
+        return torch.tensor(probs), traces
+
+    @torch.no_grad()
+    def forward_teacher_forcing(self, images: List[str], texts: List[str], fps=None, question_template: str = default_question_template,
+                                answer_template: str = default_answer_template, max_new_tokens: int = 1, temperature: float = 1.0) -> torch.Tensor:
+        """forward_with_trace_teacher_forcing's scores without the trace."""
+        scores = torch.zeros(len(images), dtype=torch.float32)
+        for i, (rows, a_ids) in enumerate(self._teacher_scores(images, texts, fps, question_template, answer_template, max_new_tokens)):
+            p = self._token_probs(rows, torch.tensor(a_ids), temperature)
+            scores[i] = float(torch.prod(p.double()) ** (1.0 / len(a_ids)))
+        return scores
 
     @staticmethod
     def _warp(scores: torch.Tensor, temperature: float, top_p: float, top_k: int = 0) -> torch.Tensor:

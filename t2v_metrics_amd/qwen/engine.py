@@ -9,7 +9,7 @@ import torch
 
 from ..engine import VqsError, VqsWeightDesc, load_library, _stream_ptr
 from .config import Qwen25VLConfig
-from .layout import shared_prefix_plan, text_layout, vision_layout
+from .layout import answer_rows, shared_prefix_plan, text_layout, vision_layout
 
 _i32, _f32, _vp, _sz = ctypes.c_int32, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
@@ -48,6 +48,10 @@ _SIGS = {
     "vqs_qwen_suffix_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "vqs_qwen_score_suffix": (_i32, [_vp] + [_vp] * 8 + [_i32, _i32, _i32, _vp, _i32, _sz, _vp, _vp, _sz, _vp]),
     "vqs_qwen_prefill_suffix": (_i32, [_vp] + [_vp] * 8 + [_i32, _i32, _i32, _vp, _i32, _sz, _vp, _vp, _sz, _vp, _sz, _i32, _vp]),
+    "vqs_qwen_score_rows_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "vqs_qwen_score_rows": (_i32, [_vp] + [_vp] * 6 + [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "vqs_qwen_suffix_rows_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32]),
+    "vqs_qwen_score_suffix_rows": (_i32, [_vp] + [_vp] * 7 + [_i32, _i32, _i32, _vp, _i32, _sz, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -314,6 +318,63 @@ class QwenEngine:
             kv = torch.empty(self.lib.vqs_qwen_kv_bytes(self._h, B, Lmax), dtype=torch.uint8, device=dev)
             self._check(self.lib.vqs_qwen_prefill_suffix(*args, kv.data_ptr(), kv.numel(), Lmax, _stream_ptr()), "vqs_qwen_prefill_suffix")
             return logits, self._decode_state(plan, kv, t["seq_len"], Lmax)
+
+    def score_rows(self, merged: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor, grids: Sequence[Tuple[int, int, int]],
+                   n_rows) -> torch.Tensor:
+        """-> fp32 [sum n_b, vocab]: logits of the LAST n_b valid positions of every sample (n_rows: one int or one per sample), in sample
+        and position order, from one pass (vqs_qwen_score_rows): teacher-forced scoring of an answer whose first n_b - 1 tokens end the
+        sequence.  Every row goes through the precise tail; n_rows = 1 is score_logits bit for bit."""
+        lay = text_layout(self.cfg, input_ids.cpu(), attention_mask.cpu(), grids)
+        B, L = input_ids.shape
+        rows = answer_rows(lay["seq_len"], n_rows, L)
+        with torch.cuda.device(self.device):
+            dev = self.device
+            Q = int(rows[0].numel())
+            ids = input_ids.to(dev, torch.int32).contiguous()
+            t = self._upload(lay, ("vis_slot", "seq_len", "cos", "sin"))
+            r = [x.to(dev) for x in rows]
+            logits = torch.empty(Q, self.cfg.text.vocab, dtype=torch.float32, device=dev)
+            self._merged_matches_mode(merged)
+            ws = self._workspace(self.lib.vqs_qwen_score_rows_workspace_bytes(self._h, B, L, Q))
+            self._check(self.lib.vqs_qwen_score_rows(self._h, merged.contiguous().data_ptr(), ids.data_ptr(), t["vis_slot"].data_ptr(),
+                                                     t["seq_len"].data_ptr(), t["cos"].data_ptr(), t["sin"].data_ptr(), B, L, r[0].data_ptr(),
+                                                     r[1].data_ptr(), r[2].data_ptr(), Q, logits.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     _stream_ptr()), "vqs_qwen_score_rows")
+            return logits
+
+    def score_rows_shared(self, merged: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor, grids: Sequence[Tuple[int, int, int]],
+                          media: Sequence, n_rows):
+        """score_rows with the prompt prefix of every medium computed once (vqs_qwen_prefix + vqs_qwen_score_suffix_rows); score_shared's
+        split rule.  Bitwise score_rows.  -> logits, or None when no medium has two samples here."""
+        plan = shared_prefix_plan(self.cfg, input_ids.cpu(), attention_mask.cpu(), grids, media)
+        if plan is None:
+            return None
+        B, L = input_ids.shape
+        U, Lp, Ls = plan["U"], plan["Lp"], plan["Ls"]
+        rows = answer_rows(plan["seq_len"], n_rows, Ls, offset=Lp)
+        with torch.cuda.device(self.device):
+            dev = self.device
+            Q = int(rows[0].numel())
+            self._merged_matches_mode(merged)
+            merged = merged.contiguous()
+            n_vis = merged.shape[0] // B
+            merged_u = merged.view(B, n_vis, -1)[plan["first"]].reshape(U * n_vis, -1).contiguous()
+            t = self._upload(plan, ("media_idx", "prefix_ids", "prefix_vis_slot", "prefix_cos", "prefix_sin", "suffix_ids", "suffix_vis_slot",
+                                    "suffix_cos", "suffix_sin", "seq_len"))
+            r = [x.to(dev) for x in rows]
+            pkv = torch.empty(self.lib.vqs_qwen_prefix_kv_bytes(self._h, U, Lp), dtype=torch.uint8, device=dev)
+            ws = self._workspace(max(self.lib.vqs_qwen_prefix_workspace_bytes(self._h, U, Lp),
+                                     self.lib.vqs_qwen_suffix_rows_workspace_bytes(self._h, B, Lp, Ls, Q)))
+            self._check(self.lib.vqs_qwen_prefix(self._h, merged_u.data_ptr(), t["prefix_ids"].data_ptr(), t["prefix_vis_slot"].data_ptr(),
+                                                 t["prefix_cos"].data_ptr(), t["prefix_sin"].data_ptr(), U, Lp, pkv.data_ptr(), pkv.numel(),
+                                                 ws.data_ptr(), ws.numel(), _stream_ptr()), "vqs_qwen_prefix")
+            logits = torch.empty(Q, self.cfg.text.vocab, dtype=torch.float32, device=dev)
+            self._check(self.lib.vqs_qwen_score_suffix_rows(self._h, merged.data_ptr(), t["suffix_ids"].data_ptr(), t["suffix_vis_slot"].data_ptr(),
+                                                            t["seq_len"].data_ptr(), t["suffix_cos"].data_ptr(), t["suffix_sin"].data_ptr(),
+                                                            t["media_idx"].data_ptr(), B, Lp, Ls, pkv.data_ptr(), U, pkv.numel(), r[0].data_ptr(),
+                                                            r[1].data_ptr(), r[2].data_ptr(), Q, logits.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                            _stream_ptr()), "vqs_qwen_score_suffix_rows")
+            return logits
 
     def decode(self, state, token_ids: torch.Tensor) -> torch.Tensor:
         """One further position per sample: token_ids long [B] (the tokens just generated; anything for stopped samples)

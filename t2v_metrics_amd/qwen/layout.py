@@ -189,3 +189,27 @@ def shared_prefix_plan(cfg: Qwen25VLConfig, input_ids: torch.Tensor, attention_m
             "suffix_cos": cos[:, Lp:].reshape(-1, half).contiguous(), "suffix_sin": sin[:, Lp:].reshape(-1, half).contiguous(),
             "seq_len": lay["seq_len"], "last_row": (torch.arange(B) * Ls + seq_len - 1 - Lp).to(torch.int32),
             "next_pos": lay["next_pos"]}
+
+
+def answer_rows(seq_len, n_rows_per_sample, L: int, offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The row list of vqs_qwen_score_rows / vqs_qwen_score_suffix_rows (include/vqs_qwen.h) for "the last n_b valid positions of sample
+    b", in sample order and, within a sample, in position order.  seq_len [B]: whole-sequence lengths; n_rows_per_sample: one int for all
+    samples or [B]; L: rows per sample of the pass (the padded length, or Ls for the suffix pass); offset: the pass's first position
+    (Lp for the suffix pass).  -> (row_index, row_sample, row_keys) int32 [sum n_b]: position p of sample b is row b * L + p - offset
+    of the pass and sees p + 1 keys."""
+    seq = [int(x) for x in torch.as_tensor(seq_len).reshape(-1).tolist()]
+    B = len(seq)
+    n = torch.as_tensor(n_rows_per_sample).reshape(-1).tolist()
+    n = [int(n[0])] * B if len(n) == 1 else [int(x) for x in n]
+    if len(n) != B:
+        raise ValueError("one row count per sample")
+    index, sample, keys = [], [], []
+    for b in range(B):
+        if n[b] < 1 or seq[b] - n[b] < offset or seq[b] > offset + L:
+            raise ValueError(f"sample {b}: {n[b]} rows of a sequence of {seq[b]} do not lie in the pass's positions [{offset}, {offset + L})")
+        for p in range(seq[b] - n[b], seq[b]):
+            index.append(b * L + p - offset)
+            sample.append(b)
+            keys.append(p + 1)
+    mk = lambda x: torch.tensor(x, dtype=torch.int32)      # noqa: E731
+    return mk(index), mk(sample), mk(keys)
