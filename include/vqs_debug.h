@@ -167,6 +167,51 @@ int vqs_debug_decoder_attention(const void* d_q, const void* d_k, const void* d_
                                 int32_t bias_ld, int32_t precise, int64_t out_plane, void* stream);
 int vqs_debug_score_head(const float* d_logits, int32_t ldl, int32_t V, const int32_t* d_labels, float* d_lp, float* d_scores, int32_t B, int32_t T,
                          int32_t* d_flags, void* stream);
+/* Single-launch test hooks of the Qwen2.5-VL prefill's glue and of the bind-time range proof (csrc/elementwise.hip, csrc/qwen_decode.hip), on caller
+ * tensors (tests/test_gpu_qwen_glue_kernels.py, profiles/qwen_glue_kernels.md): each calls ONE launcher with the caller's arguments and nothing else (no
+ * copy, no synchronisation); a launcher's refusal comes back as VQS_ERR_INVALID and nothing is launched, and so does a NULL required pointer or a
+ * non-positive size.  No kernel of this family defines an out-of-range index map: every map entry must name a row / column that exists.
+ *   vqs_debug_rmsnorm_f16s: launch_rmsnorm_f16s: x fp32 [M, D] += fp16 delta * d1 (+ fp16 delta2 * d2), written back unless store_x == 0 (one delta only);
+ *     out [M, out_ld] (out_ld = 0: D; >= D, a multiple of 4) = w * x * rsqrt(mean x^2 + eps) * osc as IEEE fp16, or bf16 with out_bf16 != 0 (the final
+ *     norm; store_x == 0 has no such form).  w bf16 [D]; D % 4 == 0.
+ *   vqs_debug_rope_qk: launch_rope_qk: q [B, Hq, S, hd] and k [B, Hk, S, hd] rotated in place in one launch (rotate-half, lanes [0, 2 half); the others
+ *     keep their bits); cos / sin fp32 [B S, half]; f16 != 0: IEEE fp16 tensors (half % 8 == 0, hd % 8 == 0, half <= 64 only), else bf16, where any
+ *     other even half takes two launches of vqs_rope's kernel.
+ *   vqs_debug_qwen_embed: launch_qwen_embed: out fp32 [rows, D] = merged row vis_slot[r] where that is >= 0 (bf16, or IEEE fp16 times unscale with
+ *     merged_f16 != 0), else embed row min(max(ids[r], 0), vocab - 1) (bf16 [vocab, D]).
+ *   vqs_debug_gather_rows_bf16: launch_gather_rows_bf16: dst [rows, dst_ld] = row map[r] of src0 (map[r] >= 0), row -map[r] - 2 of src1 (map[r] <= -2; src1
+ *     required then) or zeros (-1), columns [cols, dst_ld) zero; source rows src_ld apart; map NULL: identity.  The hook refuses rows <= 0, cols <= 0,
+ *     src_ld < cols and dst_ld < cols on the host (the launcher checks nothing).
+ *   vqs_debug_gather_cols_bf16: launch_gather_cols_bf16: dst [rows, dst_cols] = src [rows, src_ld] column cmap[c], 0 where cmap[c] < 0.
+ *   vqs_debug_gather_rows_f32: form 0: elementwise.hip's launcher (window permutation: dst [rows, cols] = src row map[r], a zero row for -1; dense rows,
+ *     src_ld must be 0 or cols), form 1: qwen_decode.hip's (the tail's embedding rows: source rows src_ld >= cols apart, no zero rows).  cols % 4 == 0.
+ *   vqs_debug_f16_to_bf16_rows: launch_f16_to_bf16_rows: dst[r][0 : cols) = bf16(fp16 src[r][0 : cols) * unscale), rows src_ld / dst_ld elements apart;
+ *     cols % 8 == 0, rows <= 65535.
+ *   vqs_debug_qwen_tail_rope_q: launch_qwen_tail_rope_q: q_out fp32 [B, Hq hd] = the first Hq hd columns of qkv fp32 [B, ld], each head rotated by table
+ *     row row[b] of cos / sin fp32 [*, half]; lanes [2 half, hd) copied.  half <= 64; the hook also refuses ld < Hq hd.
+ *   vqs_debug_rowbound: launch_rowbound: mode 0: out[j] = R sqrt(sum_k (W[j, k] g[k % g_len])^2) + |bias[j]|; mode 1: out[j] = sum_k |W[j, k]| u[k] + |bias[j]|
+ *     (u NULL: the constant *uconst).  W bf16 [N, ldw >= K], g / bias bf16, u fp32 [K]; bias and out may be NULL; *slot = max(*slot, max_j out[j]) on
+ *     the bit pattern, 0x7fc00000 once a row's bound is NaN.
+ *   vqs_debug_absmax_bf16: launch_absmax_bf16: *slot = max(*slot, R max |x[i]|) over n bf16 elements, NaN as above.
+ *   vqs_debug_gate_pair_bound: launch_gate_pair_bound: u_act[j] = rb[gate(j)] rb[up(j)] over the packed 32 | 32 blocks for j < mlp_p, 0 for [mlp_p, ld);
+ *     *slot as above.  mlp_p % 32 == 0, ld >= mlp_p. */
+int vqs_debug_rmsnorm_f16s(float* d_x, const void* d_delta, const void* d_delta2, int32_t store_x, const void* d_w, void* d_out, int32_t out_ld, int32_t M,
+                           int32_t D, float eps, float d1, float d2, float osc, int32_t out_bf16, void* stream);
+int vqs_debug_rope_qk(void* d_q, void* d_k, const float* d_cos, const float* d_sin, int32_t B, int32_t Hq, int32_t Hk, int32_t S, int32_t hd, int32_t half,
+                      int32_t f16, void* stream);
+int vqs_debug_qwen_embed(const int32_t* d_ids, const int32_t* d_vis_slot, const void* d_embed, const void* d_merged, float* d_out, int32_t rows, int32_t D,
+                         int32_t vocab, int32_t merged_f16, float unscale, void* stream);
+int vqs_debug_gather_rows_bf16(const void* d_src0, const void* d_src1, const int32_t* d_map, void* d_dst, int32_t rows, int32_t cols, int32_t src_ld,
+                               int32_t dst_ld, void* stream);
+int vqs_debug_gather_cols_bf16(const void* d_src, const int32_t* d_cmap, void* d_dst, int32_t rows, int32_t src_ld, int32_t dst_cols, void* stream);
+int vqs_debug_gather_rows_f32(const float* d_src, const int32_t* d_map, float* d_dst, int32_t rows, int32_t cols, int32_t src_ld, int32_t form, void* stream);
+int vqs_debug_f16_to_bf16_rows(const void* d_src, void* d_dst, int32_t rows, int64_t cols, int64_t src_ld, int64_t dst_ld, float unscale, void* stream);
+int vqs_debug_qwen_tail_rope_q(const float* d_qkv, int32_t ld, const float* d_cos, const float* d_sin, const int32_t* d_row, float* d_q_out, int32_t B,
+                               int32_t Hq, int32_t hd, int32_t half, void* stream);
+int vqs_debug_rowbound(const void* d_w, int64_t ldw, int32_t N, int32_t K, int32_t mode, const void* d_g, int32_t g_len, float R, const float* d_u,
+                       const float* d_uconst, const void* d_bias, float* d_out, float* d_slot, void* stream);
+int vqs_debug_absmax_bf16(const void* d_x, int64_t n, float R, float* d_slot, void* stream);
+int vqs_debug_gate_pair_bound(const float* d_rb, int32_t mlp_p, int32_t ld, float* d_u_act, float* d_slot, void* stream);
 /* Tap window: taps copy only the rows of `count` consecutive outer entries starting at `first` -- pairs for the T5 stacks
  * (rows [first*S, (first+count)*S) of an [B*S, W] tensor, the same fraction of a head-major [B, H, S, 64] or a [B*T, W] one),
  * images for the vision tower (so the window's pairs must reference images first .. first+count-1 in order, as the bench

@@ -1496,6 +1496,76 @@ int vqs_debug_norm16(int32_t kind, float* x, const void* delta, const void* delt
     return vqs::abi_code(e);
 }
 
+// ---- single-launch hooks of the Qwen2.5-VL prefill's glue and of the bind-time range proof (include/vqs_debug.h)
+int vqs_debug_rmsnorm_f16s(float* x, const void* delta, const void* delta2, int32_t store_x, const void* w, void* out, int32_t out_ld, int32_t M, int32_t D,
+                           float eps, float d1, float d2, float osc, int32_t out_bf16, void* stream) {
+    if (!x || !w || !out || M <= 0 || D <= 0 || out_ld < 0) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_rmsnorm_f16s(x, (const bf16_t*)delta, (const bf16_t*)w, (bf16_t*)out, M, D, eps, (hipStream_t)stream, (const bf16_t*)delta2,
+                                                  store_x != 0, out_ld, d1, d2, osc, out_bf16 != 0));
+}
+
+int vqs_debug_rope_qk(void* q, void* k, const float* cs, const float* sn, int32_t B, int32_t Hq, int32_t Hk, int32_t S, int32_t hd, int32_t half, int32_t f16,
+                      void* stream) {
+    if (!q || !k || !cs || !sn || B <= 0 || Hq <= 0 || Hk <= 0 || S <= 0 || hd <= 0 || half <= 0) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_rope_qk((bf16_t*)q, (bf16_t*)k, cs, sn, B, Hq, Hk, S, hd, half, (hipStream_t)stream, f16 != 0));
+}
+
+int vqs_debug_qwen_embed(const int32_t* ids, const int32_t* vis_slot, const void* embed, const void* merged, float* out, int32_t rows, int32_t D, int32_t vocab,
+                         int32_t merged_f16, float unscale, void* stream) {
+    if (!ids || !vis_slot || !embed || !merged || !out || rows <= 0 || D <= 0 || vocab <= 0) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_qwen_embed(ids, vis_slot, (const bf16_t*)embed, (const bf16_t*)merged, out, rows, D, vocab, (hipStream_t)stream,
+                                                merged_f16 != 0, unscale));
+}
+
+int vqs_debug_gather_rows_bf16(const void* src0, const void* src1, const int32_t* map, void* dst, int32_t rows, int32_t cols, int32_t src_ld, int32_t dst_ld,
+                               void* stream) {
+    if (!src0 || !dst || rows <= 0 || cols <= 0 || src_ld < cols || dst_ld < cols) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_gather_rows_bf16((const bf16_t*)src0, (const bf16_t*)src1, map, (bf16_t*)dst, rows, cols, src_ld, dst_ld, (hipStream_t)stream));
+}
+
+int vqs_debug_gather_cols_bf16(const void* src, const int32_t* cmap, void* dst, int32_t rows, int32_t src_ld, int32_t dst_cols, void* stream) {
+    if (!src || !cmap || !dst || rows <= 0 || src_ld <= 0 || dst_cols <= 0) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_gather_cols_bf16((const bf16_t*)src, cmap, (bf16_t*)dst, rows, src_ld, dst_cols, (hipStream_t)stream));
+}
+
+int vqs_debug_gather_rows_f32(const float* src, const int32_t* map, float* dst, int32_t rows, int32_t cols, int32_t src_ld, int32_t form, void* stream) {
+    if (!src || !map || !dst || rows <= 0 || cols <= 0) return VQS_ERR_INVALID;
+    if (form == 0) {        // elementwise.hip: dense rows, -1 = a zero row
+        if (src_ld != 0 && src_ld != cols) return VQS_ERR_INVALID;
+        return vqs::abi_code(vqs::launch_gather_rows_f32(src, map, dst, rows, cols, (hipStream_t)stream));
+    }
+    if (form != 1 || src_ld < cols) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_gather_rows_f32(src, map, dst, rows, cols, src_ld, (hipStream_t)stream));      // qwen_decode.hip
+}
+
+int vqs_debug_f16_to_bf16_rows(const void* src, void* dst, int32_t rows, int64_t cols, int64_t src_ld, int64_t dst_ld, float unscale, void* stream) {
+    if (!src || !dst || src_ld < cols || dst_ld < cols) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_f16_to_bf16_rows((const bf16_t*)src, (bf16_t*)dst, rows, (long long)cols, (long long)src_ld, (long long)dst_ld, unscale,
+                                                      (hipStream_t)stream));
+}
+
+int vqs_debug_qwen_tail_rope_q(const float* qkv, int32_t ld, const float* cs, const float* sn, const int32_t* row, float* q_out, int32_t B, int32_t Hq, int32_t hd,
+                               int32_t half, void* stream) {
+    if (!qkv || !cs || !sn || !row || !q_out || hd <= 0 || Hq <= 0 || (int64_t)ld < (int64_t)Hq * hd) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_qwen_tail_rope_q(qkv, ld, cs, sn, row, q_out, B, Hq, hd, half, (hipStream_t)stream));
+}
+
+int vqs_debug_rowbound(const void* W, int64_t ldw, int32_t N, int32_t K, int32_t mode, const void* g, int32_t g_len, float R, const float* u, const float* uconst,
+                       const void* bias, float* out, float* slot, void* stream) {
+    if (!W || ldw < K || (mode != 0 && mode != 1)) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_rowbound((const bf16_t*)W, (long long)ldw, N, K, mode, (const bf16_t*)g, g_len, R, u, uconst, (const bf16_t*)bias, out, slot,
+                                              (hipStream_t)stream));
+}
+
+int vqs_debug_absmax_bf16(const void* x, int64_t n, float R, float* slot, void* stream) {
+    if (n <= 0) return VQS_ERR_INVALID;
+    return vqs::abi_code(vqs::launch_absmax_bf16((const bf16_t*)x, (size_t)n, R, slot, (hipStream_t)stream));
+}
+
+int vqs_debug_gate_pair_bound(const float* rb, int32_t mlp_p, int32_t ld, float* u_act, float* slot, void* stream) {
+    return vqs::abi_code(vqs::launch_gate_pair_bound(rb, mlp_p, ld, u_act, slot, (hipStream_t)stream));
+}
+
 int vqs_normalize_u8(const void* d_u8, void* d_out, int32_t N, int32_t H, int32_t W, const float* mean3, const float* std3,
                      void* stream) {
     if (!d_u8 || !d_out || !mean3 || !std3) return VQS_ERR_INVALID;

@@ -100,6 +100,18 @@ _SIGNATURES = {
     "vqs_debug_decoder_attention": (_c_i32, [_c_vp] * 6 + [_c_i32] * 7 + [_c_i64, _c_i32, _c_i32, _c_i32, _c_i64, _c_vp]),
     "vqs_debug_score_head": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_vp, _c_vp, _c_vp, _c_i32, _c_i32, _c_vp, _c_vp]),
     "vqs_debug_norm16": (_c_i32, [_c_i32, _c_vp, _c_vp, _c_vp, _c_i32, _c_vp, _c_vp, _c_vp, _c_i32, _c_i32, ctypes.c_float, _c_i32, _c_vp]),
+    # single launches of the Qwen2.5-VL prefill's glue and of the bind-time range proof (tests/test_gpu_qwen_glue_kernels.py)
+    "vqs_debug_rmsnorm_f16s": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_i32, _c_vp, _c_vp, _c_i32, _c_i32, _c_i32] + [_c_f32] * 4 + [_c_i32, _c_vp]),
+    "vqs_debug_rope_qk": (_c_i32, [_c_vp] * 4 + [_c_i32] * 7 + [_c_vp]),
+    "vqs_debug_qwen_embed": (_c_i32, [_c_vp] * 5 + [_c_i32] * 4 + [_c_f32, _c_vp]),
+    "vqs_debug_gather_rows_bf16": (_c_i32, [_c_vp] * 4 + [_c_i32] * 4 + [_c_vp]),
+    "vqs_debug_gather_cols_bf16": (_c_i32, [_c_vp] * 3 + [_c_i32] * 3 + [_c_vp]),
+    "vqs_debug_gather_rows_f32": (_c_i32, [_c_vp] * 3 + [_c_i32] * 4 + [_c_vp]),
+    "vqs_debug_f16_to_bf16_rows": (_c_i32, [_c_vp, _c_vp, _c_i32, _c_i64, _c_i64, _c_i64, _c_f32, _c_vp]),
+    "vqs_debug_qwen_tail_rope_q": (_c_i32, [_c_vp, _c_i32, _c_vp, _c_vp, _c_vp, _c_vp] + [_c_i32] * 4 + [_c_vp]),
+    "vqs_debug_rowbound": (_c_i32, [_c_vp, _c_i64, _c_i32, _c_i32, _c_i32, _c_vp, _c_i32, _c_f32] + [_c_vp] * 6),
+    "vqs_debug_absmax_bf16": (_c_i32, [_c_vp, _c_i64, _c_f32, _c_vp, _c_vp]),
+    "vqs_debug_gate_pair_bound": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_vp, _c_vp, _c_vp]),
     "vqs_debug_gemm_form": (_c_i32, [_c_i32] * 11),
     "vqs_debug_gemm_plan": (_c_i32, [_c_vp, _c_i32, _c_vp]),
     "vqs_debug_gemm_batched": (_c_i32, [_c_vp, _c_vp, _c_vp] + [_c_i32] * 8 + [_c_i64] * 4 + [_c_i32, _c_i32, _c_vp]),

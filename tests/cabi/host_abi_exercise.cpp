@@ -93,6 +93,55 @@ int main() {
         assert(vqs_debug_gemm_batched(&dummy2, &dummy2, &dummy2, 128, 608, 4096, 4096, 4096, 640, 5, 256, 0, 0, 0, 0, 0, 3, nullptr) == VQS_ERR_INVALID);   // gated: not a batched debug epilogue
         assert(vqs_debug_gemm_batched(&dummy2, &dummy2, &dummy2, 128, 608, 4096, 4096, 4096, 640, 3, 0, 0, 0, 0, 0, 0, 3, nullptr) == VQS_ERR_INVALID);     // batch < 1
     }
+    {   // the single-launch hooks of the Qwen2.5-VL prefill's glue and of the range proof: every refusal is host code, before any device call
+        int d = 0;
+        float f = 0.f;
+        const int I = VQS_ERR_INVALID;
+        // scaled RMSNorm: null operands, D % 4, a pitch below D or off the 4-element grid, the unstored form with a bf16 operand, delta2 without delta
+        assert(vqs_debug_rmsnorm_f16s(nullptr, nullptr, nullptr, 1, &d, &d, 0, 4, 1280, 1e-6f, 1.f, 1.f, 1.f, 0, nullptr) == I);
+        assert(vqs_debug_rmsnorm_f16s(&f, nullptr, nullptr, 1, nullptr, &d, 0, 4, 1280, 1e-6f, 1.f, 1.f, 1.f, 0, nullptr) == I);
+        assert(vqs_debug_rmsnorm_f16s(&f, nullptr, nullptr, 1, &d, nullptr, 0, 4, 1280, 1e-6f, 1.f, 1.f, 1.f, 0, nullptr) == I);
+        assert(vqs_debug_rmsnorm_f16s(&f, nullptr, nullptr, 1, &d, &d, 0, 0, 1280, 1e-6f, 1.f, 1.f, 1.f, 0, nullptr) == I);
+        assert(vqs_debug_rmsnorm_f16s(&f, nullptr, nullptr, 1, &d, &d, 0, 4, 1282, 1e-6f, 1.f, 1.f, 1.f, 0, nullptr) == I);
+        assert(vqs_debug_rmsnorm_f16s(&f, nullptr, nullptr, 1, &d, &d, 1276, 4, 1280, 1e-6f, 1.f, 1.f, 1.f, 0, nullptr) == I);
+        assert(vqs_debug_rmsnorm_f16s(&f, nullptr, nullptr, 1, &d, &d, 1282, 4, 1280, 1e-6f, 1.f, 1.f, 1.f, 0, nullptr) == I);
+        assert(vqs_debug_rmsnorm_f16s(&f, &d, nullptr, 0, &d, &d, 0, 4, 1280, 1e-6f, 1.f, 1.f, 1.f, 1, nullptr) == I);
+        assert(vqs_debug_rmsnorm_f16s(&f, nullptr, &d, 1, &d, &d, 0, 4, 1280, 1e-6f, 1.f, 1.f, 1.f, 0, nullptr) == I);
+        assert(vqs_debug_rmsnorm_f16s(&f, &d, &d, 0, &d, &d, 0, 4, 1280, 1e-6f, 1.f, 1.f, 1.f, 0, nullptr) == I);
+        // rope_qk: an fp16 half off the 16-byte grid, an odd half, a rotation wider than the head
+        assert(vqs_debug_rope_qk(nullptr, &d, &f, &f, 2, 4, 2, 33, 128, 64, 0, nullptr) == I && vqs_debug_rope_qk(&d, &d, nullptr, &f, 2, 4, 2, 33, 128, 64, 0, nullptr) == I);
+        assert(vqs_debug_rope_qk(&d, &d, &f, &f, 2, 4, 2, 33, 128, 36, 1, nullptr) == I && vqs_debug_rope_qk(&d, &d, &f, &f, 2, 4, 2, 33, 128, 41, 0, nullptr) == I);
+        assert(vqs_debug_rope_qk(&d, &d, &f, &f, 2, 4, 2, 33, 128, 72, 0, nullptr) == I && vqs_debug_rope_qk(&d, &d, &f, &f, 2, 4, 0, 33, 128, 64, 0, nullptr) == I);
+        assert(vqs_debug_qwen_embed(nullptr, &d, &d, &d, &f, 4, 128, 16, 0, 1.f, nullptr) == I && vqs_debug_qwen_embed(&d, nullptr, &d, &d, &f, 4, 128, 16, 0, 1.f, nullptr) == I);
+        assert(vqs_debug_qwen_embed(&d, &d, &d, &d, &f, 0, 128, 16, 0, 1.f, nullptr) == I && vqs_debug_qwen_embed(&d, &d, &d, &d, &f, 4, 128, 0, 0, 1.f, nullptr) == I);
+        // the gathers check nothing themselves: the hook refuses null tensors, empty shapes and a pitch narrower than the row
+        assert(vqs_debug_gather_rows_bf16(nullptr, nullptr, nullptr, &d, 4, 64, 64, 64, nullptr) == I && vqs_debug_gather_rows_bf16(&d, nullptr, nullptr, nullptr, 4, 64, 64, 64, nullptr) == I);
+        assert(vqs_debug_gather_rows_bf16(&d, nullptr, nullptr, &d, 0, 64, 64, 64, nullptr) == I && vqs_debug_gather_rows_bf16(&d, nullptr, nullptr, &d, 4, 0, 64, 64, nullptr) == I);
+        assert(vqs_debug_gather_rows_bf16(&d, nullptr, nullptr, &d, 4, 64, 64, 63, nullptr) == I && vqs_debug_gather_rows_bf16(&d, nullptr, nullptr, &d, 4, 64, 63, 64, nullptr) == I);
+        assert(vqs_debug_gather_cols_bf16(nullptr, &d, &d, 4, 64, 32, nullptr) == I && vqs_debug_gather_cols_bf16(&d, nullptr, &d, 4, 64, 32, nullptr) == I &&
+               vqs_debug_gather_cols_bf16(&d, &d, nullptr, 4, 64, 32, nullptr) == I);
+        assert(vqs_debug_gather_cols_bf16(&d, &d, &d, 0, 64, 32, nullptr) == I && vqs_debug_gather_cols_bf16(&d, &d, &d, 4, 64, 0, nullptr) == I);
+        assert(vqs_debug_gather_rows_f32(nullptr, &d, &f, 4, 64, 64, 0, nullptr) == I && vqs_debug_gather_rows_f32(&f, nullptr, &f, 4, 64, 64, 1, nullptr) == I);
+        assert(vqs_debug_gather_rows_f32(&f, &d, &f, 0, 64, 64, 0, nullptr) == I && vqs_debug_gather_rows_f32(&f, &d, &f, 4, 0, 64, 1, nullptr) == I);
+        assert(vqs_debug_gather_rows_f32(&f, &d, &f, 4, 64, 64, 2, nullptr) == I && vqs_debug_gather_rows_f32(&f, &d, &f, 4, 64, 68, 0, nullptr) == I);     // no such form; form 0 is dense
+        assert(vqs_debug_gather_rows_f32(&f, &d, &f, 4, 66, 66, 0, nullptr) == I && vqs_debug_gather_rows_f32(&f, &d, &f, 4, 66, 68, 1, nullptr) == I);     // cols % 4
+        assert(vqs_debug_gather_rows_f32(&f, &d, &f, 4, 64, 60, 1, nullptr) == I && vqs_debug_gather_rows_f32(&f, &d, &f, 4, 64, 66, 1, nullptr) == I);     // src_ld < cols, src_ld % 4
+        assert(vqs_debug_f16_to_bf16_rows(nullptr, &d, 4, 128, 128, 256, 1.f, nullptr) == I && vqs_debug_f16_to_bf16_rows(&d, nullptr, 4, 128, 128, 256, 1.f, nullptr) == I);
+        assert(vqs_debug_f16_to_bf16_rows(&d, &d, 4, 124, 128, 256, 1.f, nullptr) == I && vqs_debug_f16_to_bf16_rows(&d, &d, 65536, 128, 128, 256, 1.f, nullptr) == I);
+        assert(vqs_debug_f16_to_bf16_rows(&d, &d, 0, 128, 128, 256, 1.f, nullptr) == I && vqs_debug_f16_to_bf16_rows(&d, &d, 4, 128, 128, 120, 1.f, nullptr) == I);
+        assert(vqs_debug_qwen_tail_rope_q(nullptr, 1024, &f, &f, &d, &f, 2, 4, 128, 64, nullptr) == I && vqs_debug_qwen_tail_rope_q(&f, 1024, &f, &f, nullptr, &f, 2, 4, 128, 64, nullptr) == I);
+        assert(vqs_debug_qwen_tail_rope_q(&f, 1024, &f, &f, &d, &f, 2, 4, 256, 72, nullptr) == I && vqs_debug_qwen_tail_rope_q(&f, 1024, &f, &f, &d, &f, 2, 4, 64, 40, nullptr) == I);
+        assert(vqs_debug_qwen_tail_rope_q(&f, 1024, &f, &f, &d, &f, 0, 4, 128, 64, nullptr) == I && vqs_debug_qwen_tail_rope_q(&f, 500, &f, &f, &d, &f, 2, 4, 128, 64, nullptr) == I);
+        // range proof: empty shapes, a mode without its operands, no slot, a pitch below K
+        assert(vqs_debug_rowbound(nullptr, 64, 4, 64, 0, &d, 64, 1.f, nullptr, nullptr, nullptr, &f, &f, nullptr) == I && vqs_debug_rowbound(&d, 64, 0, 64, 0, &d, 64, 1.f, nullptr, nullptr, nullptr, &f, &f, nullptr) == I);
+        assert(vqs_debug_rowbound(&d, 64, 4, 0, 0, &d, 64, 1.f, nullptr, nullptr, nullptr, &f, &f, nullptr) == I && vqs_debug_rowbound(&d, 64, 4, 64, 0, nullptr, 64, 1.f, nullptr, nullptr, nullptr, &f, &f, nullptr) == I);
+        assert(vqs_debug_rowbound(&d, 64, 4, 64, 0, &d, 0, 1.f, nullptr, nullptr, nullptr, &f, &f, nullptr) == I && vqs_debug_rowbound(&d, 64, 4, 64, 1, nullptr, 0, 0.f, nullptr, nullptr, nullptr, &f, &f, nullptr) == I);
+        assert(vqs_debug_rowbound(&d, 64, 4, 64, 1, nullptr, 0, 0.f, &f, nullptr, nullptr, &f, nullptr, nullptr) == I && vqs_debug_rowbound(&d, 60, 4, 64, 1, nullptr, 0, 0.f, &f, nullptr, nullptr, &f, &f, nullptr) == I);
+        assert(vqs_debug_rowbound(&d, 64, 4, 64, 2, &d, 64, 1.f, &f, nullptr, nullptr, &f, &f, nullptr) == I);
+        assert(vqs_debug_absmax_bf16(nullptr, 64, 1.f, &f, nullptr) == I && vqs_debug_absmax_bf16(&d, 0, 1.f, &f, nullptr) == I && vqs_debug_absmax_bf16(&d, 64, 1.f, nullptr, nullptr) == I);
+        assert(vqs_debug_gate_pair_bound(nullptr, 32, 32, &f, &f, nullptr) == I && vqs_debug_gate_pair_bound(&f, 48, 64, &f, &f, nullptr) == I && vqs_debug_gate_pair_bound(&f, 64, 32, &f, &f, nullptr) == I);
+        assert(vqs_debug_gate_pair_bound(&f, 0, 32, &f, &f, nullptr) == I && vqs_debug_gate_pair_bound(&f, 32, 32, nullptr, &f, nullptr) == I && vqs_debug_gate_pair_bound(&f, 32, 32, &f, nullptr, nullptr) == I);
+    }
     assert(vqs_debug_gemm_form(400000, 4096, 10240, 10240, 10240, 3, 1, 3, 0, 0, 0) == 0 && vqs_debug_gemm_form(400000, 4096, 10240, 10240, 10240, 3, 2, 3, 0, 0, 0) == -1);
     int64_t ld = 0;
     assert(vqs_workspace_offset(h, "logits", 4, 33, 2, &ld) >= 0 && ld == 32128);
